@@ -2,11 +2,20 @@
 """
 bench.py -- output-map Mpixels/s of the UMPA matching path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C1|C5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C1|C5] [--full] [--dump-outputs DIR]
 
 One "step" is one pass of the hot path over one synthetic stack: every output pixel of the frame is matched.
 Inputs are resident in HBM before the timed region starts, outputs stay in HBM (the PCIe-inclusive rate of the
-host-array API is quoted in DESIGN.md, never here).
+host-array API is quoted in DESIGN.md, never here).  The inputs are generated from fixed seeds: the same arguments
+give the same inputs on every run.
+
+A plain run sets up, warms up, times K steps and prints the result line.  Everything else the benchmark measures or
+checks runs only with --full: the per-kernel HIP-event timing and the roofline, the evaluation-count statistics of one
+more untimed step, the cpu_baseline leg (unless --no-cpu) and, N > 1, the check of the gathered maps (`gpu_agrees`).
+
+--dump-outputs DIR writes the maps the timed path left in its last step as DIR/<key>.npy (the result keys of
+model.match: f, T, dx, dy[, df] in float64, err in float32), at most DUMP_BYTES in all: larger maps are written at a
+fixed, seeded sample of pixels whose flat row-major indices go to DIR/pixel_index.npy.
 
 N = 1   BASELINE config C2 (2048x2048, 10 frames, Nw=5, max_shift=5, dark-field on): one `umpa_hip_match_region`
         (include/umpa_hip.h) per step.  `--config C5` times the step-scan farm shape instead (umpa_amd/farm.py).
@@ -21,7 +30,7 @@ N > 1   (launched by torch.distributed.run, one rank per GPU, RCCL) BASELINE con
              RCCL send/recv group per piece) as soon as its kernels are enqueued, overlapping the next piece.
         Per-GPU work is the same for every N (weak scaling); `value` counts the output pixels of the whole image.
 
-Rank 0 prints ONE JSON line (see the driver contract), including
+Rank 0 prints ONE JSON line (see the driver contract), including (--full; null otherwise)
   "roofline":     the dominant kernel against the roofline that bounds it (fp64 FMA; the HBM figure beside it)
   "cpu_baseline": the reference C++ core (oracle/_ref, kind "reference") or this repo's C restatement (kind "port")
                   timed on the host cores on a bounded row sample, N = 1 only -- and the GPU maps of those rows are
@@ -53,6 +62,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_PEAK_TF = 78.6            # fp64 vector = fp64 MFMA peak on MI355X: 256 CU x 64 FMA/clk x 2.4 GHz x 2 (public spec)
 BLOCK_ROWS = 1024              # input rows per rank of the row-sharded image (8 x 1024 = BASELINE config C4)
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: all .npy files of a run together stay below this
 
 
 def parse():
@@ -63,9 +73,39 @@ def parse():
     ap.add_argument("--config", default=None, help="N=1: C2 (default), C1, C3, C5, C2mask / C2maskNoDF (C2's stack with a 95 %% random mask); N>1: C4")
     ap.add_argument("--rows", type=int, default=0, help="override frame height (debugging)")
     ap.add_argument("--cols", type=int, default=0, help="override frame width (debugging)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: per-kernel timing and roofline, "
+                         "evaluation-count statistics, the cpu_baseline leg, gpu_agrees")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg and the gpu_agrees check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the maps of the last timed step as DIR/<key>.npy (a seeded pixel sample beyond %d MB)" % (DUMP_BYTES // 10 ** 6))
     ap.add_argument("--force", choices=["auto", "direct", "tiled"], default="auto")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config == "C5":
+        ap.error("--dump-outputs is not offered for --config C5 (its maps go to the host inside farm.bench_c5)")
+    return args
+
+
+def dump_outputs(out_dir, values, err, keys):
+    """--dump-outputs: the maps of the last timed step (device tensors: ``values`` [N0, N1, nparam] float64 in the plane
+    order ``keys``, ``err`` [N0, N1] int32) as out_dir/<key>.npy + out_dir/err.npy (float32).  Maps of more than DUMP_BYTES
+    in all are written at a fixed, seeded sample of pixels (1-D arrays), their flat row-major indices as pixel_index.npy."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    N0, N1, nparam = values.shape[0], values.shape[1], len(keys)
+    vals, errs = values[:N0, :N1, :nparam], err[:N0, :N1]
+    if N0 * N1 * (8 * nparam + 4) > DUMP_BYTES - 4096:                # (4096: the .npy headers)
+        n = (DUMP_BYTES - 4096) // (8 * nparam + 4 + 8)
+        idx = np.sort(np.random.default_rng(20261016).choice(N0 * N1, size=n, replace=False))
+        sel = torch.from_numpy(idx).to(values.device)
+        vals, errs = vals.reshape(-1, nparam)[sel], errs.reshape(-1)[sel]
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    v = vals.cpu().numpy()
+    for q, k in enumerate(keys):
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v[..., q], dtype=np.float64))
+    np.save(os.path.join(out_dir, "err.npy"), errs.cpu().numpy().astype(np.float32))
 
 
 def algorithmic_bytes(K, H, W, N0, N1, nparam):
@@ -225,32 +265,18 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    lib.timing_enable(h, 1)
+    if args.full:
+        lib.timing_enable(h, 1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    lib.timing_enable(h, 0)
-    kernels = collect_kernels(lib, h)
     path = {1: "direct", 2: "tiled", 3: "direct-staged"}.get(lib.last_path(h), "?")
     if masked and path == "tiled":
         path = "tiled (corr_masked + replay_cost)"
-
-    step(with_ncalls=True)                                  # untimed: evaluation-count statistics of this dataset
-    torch.cuda.synchronize()
-    st4 = (ctypes.c_double * 4)()
-    lib.check(lib.last_stats(h, st4), "last_stats")         # on-demand passes of the shift table (umpa_ondemand.h)
-    nc = ncalls.cpu().numpy()
-    err_h = err.cpu().numpy()
-
-    # (the PMC traffic figures belong to a geometry: an overridden frame shape has none, except one rank's slab of C4)
-    tkey = config if not (args.rows or args.cols) else ("C4slab" if (config, args.rows, args.cols) == ("C2", 1042, 8192) else "")
-    roof = roofline(kernels, args.steps, algorithmic_bytes(K, H, W, N0, N1, nparam), tkey,
-                    useful=None if mask is not None else useful_fma(K, Nw, ms, N0, N1), ms_per_step=dt / args.steps * 1e3)
-    cpu = None
-    if not args.no_cpu:
-        cpu = cpu_baseline(m, sam, ref, Nw, ms, df, N0, N1, mask=mask)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, values, err, ("f", "T", "dx", "dy", "df")[:nparam])
     out = {
         "metric": "Mpixels/s (output map) at Nw=%d, max_shift=%d, %d frames" % (Nw, ms, K),
         "value": round(npx * args.steps / dt / 1e6, 3),
@@ -262,15 +288,32 @@ def main():
         "config": {"workload": "%s: %dx%d, %d frames, Nw=%d, max_shift=%d, dark-field %s" % (
                        config, H, W, K, Nw, ms, "on" if df else "off"),
                    "mask": "95 % random 0/1 mask per frame (model.pyx:257-262)" if masked else None,
-                   "output_pixels_per_gpu": npx, "kernel_path": path,
-                   "Ncalls_mean": round(float(nc.mean()), 3), "Ncalls_p99": int(np.percentile(nc, 99)),
-                   "err_ok_fraction": round(float(err_h.mean()), 5), "parallelism": "1 GPU",
-                   "table_passes_computed": int(st4[0]), "table_passes_exhaustive": int(st4[1]),
-                   "pixels_replayed_twice": int(st4[2]), "tiles_repaired": int(st4[3]),
+                   "output_pixels_per_gpu": npx, "kernel_path": path, "parallelism": "1 GPU",
                    "input_generation_s": round(t_gen, 1)},
-        "roofline": roof,
-        "cpu_baseline": cpu,
+        "roofline": None,
+        "cpu_baseline": None,
     }
+    if args.full:
+        lib.timing_enable(h, 0)
+        kernels = collect_kernels(lib, h)
+        step(with_ncalls=True)                              # untimed: evaluation-count statistics of this dataset
+        torch.cuda.synchronize()
+        st4 = (ctypes.c_double * 4)()
+        lib.check(lib.last_stats(h, st4), "last_stats")     # on-demand passes of the shift table (umpa_ondemand.h)
+        nc = ncalls.cpu().numpy()
+        err_h = err.cpu().numpy()
+        out["config"].update({"Ncalls_mean": round(float(nc.mean()), 3), "Ncalls_p99": int(np.percentile(nc, 99)),
+                              "err_ok_fraction": round(float(err_h.mean()), 5),
+                              "table_passes_computed": int(st4[0]), "table_passes_exhaustive": int(st4[1]),
+                              "pixels_replayed_twice": int(st4[2]), "tiles_repaired": int(st4[3])})
+
+        # (the PMC traffic figures belong to a geometry: an overridden frame shape has none, except one rank's slab of C4)
+        tkey = config if not (args.rows or args.cols) else ("C4slab" if (config, args.rows, args.cols) == ("C2", 1042, 8192) else "")
+        out["roofline"] = roofline(kernels, args.steps, algorithmic_bytes(K, H, W, N0, N1, nparam), tkey,
+                                   useful=None if mask is not None else useful_fma(K, Nw, ms, N0, N1),
+                                   ms_per_step=dt / args.steps * 1e3)
+        if not args.no_cpu:
+            out["cpu_baseline"] = cpu_baseline(m, sam, ref, Nw, ms, df, N0, N1, mask=mask)
     print(json.dumps(out), flush=True)
 
 
@@ -392,7 +435,8 @@ def sharded(args, world, rank, local, dev, backend):
     for _ in range(max(args.warmup - 1, 0)):
         step()
     fence()
-    lib.timing_enable(h, 1)
+    if args.full:
+        lib.timing_enable(h, 1)
     t0 = time.perf_counter()
     for s in range(args.steps):
         step(ev[s])
@@ -403,20 +447,17 @@ def sharded(args, world, rank, local, dev, backend):
     tmax = torch.tensor([dt] + list(phases), dtype=torch.float64, device=coll)
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax[0].item())
-    kernels = collect_kernels(lib, h)
     path = {1: "direct", 2: "tiled", 3: "direct-staged"}.get(lib.last_path(h), "?")
-    step(with_ncalls=True)
-    torch.cuda.synchronize()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, whole_v, whole_e, ("f", "T", "dx", "dy", "df")[:nparam])
+    if args.full:
+        kernels = collect_kernels(lib, h)
+        step(with_ncalls=True)
+        torch.cuda.synchronize()
 
     if rank == 0:
-        nc = ncalls.cpu().numpy()
-        err_all = whole_e.cpu().numpy()
         npx = n_out * N1
-        agrees = None if args.no_cpu else verify_slab_boundaries(
-            world, H, W, K, Nw, ms, df, P, N1, nparam, st_s, whole_v, whole_e, cls, local)
         name = "C4" if (world == 8 and H == 8192 and W == 8192) else "C4-type"
-        roof = roofline(kernels, args.steps, algorithmic_bytes(K, N0 + 2 * P, W, N0, N1, nparam), "C4slab",
-                        useful=useful_fma(K, Nw, ms, N0, N1), ms_per_step=dt / args.steps * 1e3)   # (rank 0's slab over the whole step)
         out = {
             "metric": "Mpixels/s (output map) at Nw=%d, max_shift=%d, %d frames" % (Nw, ms, K),
             "value": round(npx * args.steps / dt / 1e6, 3),
@@ -438,13 +479,20 @@ def sharded(args, world, rank, local, dev, backend):
                                       "after the match" % piece_rows if overlap else "after the match",
                        "halo_bytes_received_per_rank": st_s.halo_bytes() + st_r.halo_bytes(),
                        "gather_bytes_to_rank0": int((biggest * N1 * (nparam * 8 + 4)) * (world - 1)),
-                       "Ncalls_mean_rank0": round(float(nc.mean()), 3),
-                       "err_ok_fraction": round(float(err_all.mean()), 5),
                        "input_generation_s": round(t_gen, 1)},
-            "roofline": roof,
+            "roofline": None,
             "cpu_baseline": None,
-            "gpu_agrees": agrees,
+            "gpu_agrees": None,
         }
+        if args.full:
+            out["config"].update({"Ncalls_mean_rank0": round(float(ncalls.cpu().numpy().mean()), 3),
+                                  "err_ok_fraction": round(float(whole_e.cpu().numpy().mean()), 5)})
+            out["roofline"] = roofline(kernels, args.steps, algorithmic_bytes(K, N0 + 2 * P, W, N0, N1, nparam), "C4slab",
+                                       useful=useful_fma(K, Nw, ms, N0, N1),
+                                       ms_per_step=dt / args.steps * 1e3)                # (rank 0's slab over the whole step)
+            if not args.no_cpu:
+                out["gpu_agrees"] = verify_slab_boundaries(world, H, W, K, Nw, ms, df, P, N1, nparam, st_s, whole_v, whole_e,
+                                                           cls, local)
         print(json.dumps(out), flush=True)
     dist.barrier()
     dist.destroy_process_group()
@@ -496,7 +544,7 @@ def verify_slab_boundaries(world, H, W, K, Nw, ms, df, P, N1, nparam, st, whole_
 # ------------------------------------------------------------------------------------------------
 def farm_bench(args, local):
     from umpa_amd import farm
-    if args.no_cpu:
+    if not args.full or args.no_cpu:
         print(json.dumps(farm.bench_c5(device=local, steps=args.steps, warmup=args.warmup)), flush=True)
         return
     # one projection of the series against the CPU checker: a band of full-width rows of its maps, held to the parity bar

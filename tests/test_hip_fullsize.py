@@ -6,7 +6,7 @@ size-independent properties -- the CPU oracle would need minutes per case here:
     the reference's own term order) must produce the same walk for all 4.1 Mpx and the same maps;
   * an exactly translated, scaled stack must come back as that integer shift, T = scale, df = 1;
   * ROI / step results are slices of the full result (pixels are independent).
-bench.py additionally compares the GPU maps with the reference C++ core on every run (`gpu_agrees`).
+bench.py --full additionally compares the GPU maps with the reference C++ core on every run (`gpu_agrees`).
 """
 import numpy as np
 import pytest

@@ -361,7 +361,7 @@ def test_bench_sharded_leg_rehearsal(tmp_path, gather):
     env = dict(os.environ, UMPA_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", UMPA_BENCH_GATHER=gather)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--rows", "128", "--cols", "512"]
+           "--rows", "128", "--cols", "512", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -1,6 +1,6 @@
 import ctypes, os, sys, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from umpa_amd import _lib, model
 from umpa_amd.synth import make_stack

@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out/trace_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d "$OUT" -o run -- python3 "$ROOT/bench.py" --no-cpu --steps 2 --warmup 1 "$@" > "$OUT/log.txt" 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$OUT" -o run -- python3 "$ROOT/bench.py" --full --no-cpu --steps 2 --warmup 1 "$@" > "$OUT/log.txt" 2>&1
 cd "$ROOT"
 python3 - "$OUT" > "$ROOT/gpurun_out/trace_$TAG.txt" <<'PY'
 import csv, glob, sys
