@@ -532,7 +532,7 @@ def test_masked_models_against_the_oracle(hip_ns, port_ns, cfg):
     dict(H=330, W=400, K=4, Nw=4, ms=5, df=True, amp=3.5, assign="sam", mask=True, mk=dict()),
     dict(H=330, W=400, K=4, Nw=4, ms=5, df=False, amp=3.5, assign="ref", mask=True, mk=dict(step=2)),
     # windows of 13 / 15 pixels: corr_march's units are (strip, band, pass); the prediction is a lattice of sample pixels
-    # (od_run_chunk_march); bands of 64 rows so that these small images have several
+    # (od_run_chunk_lattice); bands of 64 rows so that these small images have several
     dict(H=420, W=520, K=4, Nw=7, ms=8, df=True, amp=6.0, assign="sam", mask=False, mk=dict(), march_rows=64),
     dict(H=380, W=300, K=3, Nw=6, ms=6, df=False, amp=4.5, assign="ref", mask=False, mk=dict(step=2, dxdy=(1, -1)), march_rows=64),
     dict(H=300, W=410, K=5, Nw=7, ms=10, df=True, amp=7.5, assign="ref", mask=False, mk=dict(), march_rows=96),
@@ -552,12 +552,8 @@ def test_on_demand_table_passes_change_nothing(hip_ns, monkeypatch, cfg):
     out, stats = {}, {}
     if "march_rows" in cfg:
         monkeypatch.setenv("UMPA_HIP_MARCH_OD_ROWS", str(cfg["march_rows"]))
-    for od in ("0", "1", "lattice"):
-        # "lattice": corr_volume's / corr_masked's stages with the sample-lattice prediction (corr_march's only one) instead of seed tiles
-        if od == "lattice" and "march_rows" in cfg:
-            continue
-        monkeypatch.setenv("UMPA_HIP_ONDEMAND", "0" if od == "0" else "1")
-        monkeypatch.setenv("UMPA_HIP_OD_PRED", "lattice" if od == "lattice" else "seed")
+    for od in ("0", "1"):
+        monkeypatch.setenv("UMPA_HIP_ONDEMAND", od)
         m = cls(sam, ref, mask_list=mask, window_size=cfg["Nw"], max_shift=cfg["ms"])
         m.assign_coordinates = cfg["assign"]
         m._force = _lib.F_FORCE_TILED

@@ -110,12 +110,8 @@ int main(int argc, char** argv)
     A.da = SPB > 1 ? 2 * SPB : LA + 1; A.db = SPB > 1 ? nuy - 1 + 2 * SPB : nuy + LA;
     const bool sam_is_A = sigma > 0;
     A.baseA = (const char*)(sam_is_A ? dsam : dref); A.baseB = (const char*)(sam_is_A ? dref : dsam);
-    std::vector<unsigned> foff(2 * K);
-    for (int k = 0; k < K; k++) { foff[k] = (unsigned)(k * plane * 8); foff[K + k] = (unsigned)(k * plane * 8); }
-    unsigned* dfoff;
-    CK(hipMalloc(&dfoff, 2 * K * 4));
-    CK(hipMemcpy(dfoff, foff.data(), 2 * K * 4, hipMemcpyHostToDevice));
-    A.frame_off = dfoff;
+    if (K > UMPA_MARCH_KMAX) { printf("%d frames: corr_march stages at most %d\n", K, UMPA_MARCH_KMAX); return 1; }
+    for (int k = 0; k < K; k++) { A.frame_off[k] = (unsigned)(k * plane * 8); A.frame_off[K + k] = (unsigned)(k * plane * 8); }
     A.ablate = ablate;
     const size_t lds = (size_t)A.da * A.a_slot + (size_t)A.db * A.b_slot;
     const int nitems = A.nstrips * A.nbands, grid = 8 * ((nitems + 7) / 8) * A.npass;

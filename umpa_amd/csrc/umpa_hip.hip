@@ -59,8 +59,6 @@ struct DevBuf {                       // grow-only device scratch
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-struct TimedLaunch { int name; hipEvent_t t0, t1; double fma; const int* counts; double fma_per; };
-
 } // namespace
 
 struct umpa_hip_model {
@@ -244,19 +242,9 @@ bool staged_geometry(const umpa_hip_model* m, const RegionArgs& A, StagedGeom& G
 template <int KIND, bool MASK, int NWC>
 hipError_t launch_staged_nw(umpa_hip_model* m, const RegionArgs& A, const StagedGeom& G, size_t lds_bytes, hipStream_t s)
 {
-    static bool attr_set[64] = {};
-    int devid = 0;
-    (void)hipGetDevice(&devid);
-    {
-        std::lock_guard<std::mutex> lock(tiled_attr_mutex());
-        if (!attr_set[devid & 63]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&match_staged_kernel<KIND, MASK, NWC>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)(UMPA_LDS_BUDGET - 25 * UMPA_STAGED_THREADS * sizeof(double) - 1024));
-            if (e != hipSuccess) return e;
-            attr_set[devid & 63] = true;
-        }
-    }
+    const hipError_t e = set_lds_limit_once<&match_staged_kernel<KIND, MASK, NWC>>(
+        (int)(UMPA_LDS_BUDGET - 25 * UMPA_STAGED_THREADS * sizeof(double) - 1024), current_device());
+    if (e != hipSuccess) return e;
     const int nbx = (A.N1 + UMPA_STAGED_BX - 1) / UMPA_STAGED_BX, nby = (A.N0 + UMPA_STAGED_BY - 1) / UMPA_STAGED_BY;
     const int grid = ((nbx * nby + 7) / 8) * 8;
     ScopedTimer t(m, s, KN_STAGED);
@@ -336,17 +324,9 @@ int run_direct(umpa_hip_model* m, const RegionArgs& A0, hipStream_t s, int flags
             const BlurTileGeom BG = blur_tile_geometry(halo, C.step0, C.step1);
             const size_t blur_lds = (size_t)BG.PR * BG.PC * sizeof(double) * (m->has_mask ? 2 : 1);
             if (!no_reuse && !no_tiles && blur_lds <= (size_t)UMPA_LDS_BUDGET / 2) {
-                static bool battr[2][64] = {};
-                {
-                    std::lock_guard<std::mutex> lock(tiled_attr_mutex());
-                    if (!battr[m->has_mask][m->device & 63]) {
-                        hipError_t be = m->has_mask
-                            ? hipFuncSetAttribute(reinterpret_cast<const void*>(&blur_tiles_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, UMPA_LDS_BUDGET / 2)
-                            : hipFuncSetAttribute(reinterpret_cast<const void*>(&blur_tiles_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, UMPA_LDS_BUDGET / 2);
-                        if (be != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "blur_tiles attribute: %s", hipGetErrorString(be));
-                        battr[m->has_mask][m->device & 63] = true;
-                    }
-                }
+                const hipError_t be = m->has_mask ? set_lds_limit_once<&blur_tiles_kernel<true>>(UMPA_LDS_BUDGET / 2, m->device)
+                                                  : set_lds_limit_once<&blur_tiles_kernel<false>>(UMPA_LDS_BUDGET / 2, m->device);
+                if (be != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "blur_tiles attribute: %s", hipGetErrorString(be));
                 dim3 bgrid((C.N1 + UMPA_BLURT_BX - 1) / UMPA_BLURT_BX, (C.N0 + UMPA_BLURT_BY - 1) / UMPA_BLURT_BY), bblk(UMPA_BLURT_BX, UMPA_BLURT_BY);
                 {
                     ScopedTimer t(m, s, KN_BLUR);
@@ -463,8 +443,7 @@ struct FrameSubset { const FrameDesc* frames; int n; FrameBox box; const FrameDe
 int run_tiled(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int flags, hipStream_t s,
               int piece_rows, const std::function<void(int, int)>& on_rows, const FrameSubset* sub = nullptr)
 {
-    TiledTimers tt;
-    tt.get = [m]() { return get_event(m); };
+    TiledTimers tt(m->timing ? &m->launches : nullptr, [m]() { return get_event(m); }, s);
     ModelDev dev = m->dev();
     if (sub) { dev.frames = sub->frames; dev.Na = sub->n; m->tiled.ref_maps_ok = false; }      // (Nwt stays the model's frame count)
     const bool reuse = !sub && (flags & UMPA_HIP_F_REUSE_REF_MAPS) != 0;
@@ -479,13 +458,12 @@ int run_tiled(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int fla
     }
     int rc = m->has_mask
         ? tiled_match_masked(m->tiled, dev, m->kind, g.Himg, g.Wimg, sub ? sub->box : g.box, A, s,
-                             m->timing ? &tt : nullptr, reuse, m->mask_binary, piece_rows, on_rows)
+                             tt, reuse, m->mask_binary, piece_rows, on_rows)
         : tiled_match(m->tiled, dev, m->kind, g.Himg, g.Wimg, sub ? sub->box : g.box, A, s,
-                      m->timing ? &tt : nullptr, reuse, piece_rows, on_rows, sub ? sub->host : hf.data());
+                      tt, reuse, piece_rows, on_rows, sub ? sub->host : hf.data());
     if (sub) m->tiled.ref_maps_ok = false;                            // the maps now hold a subset's planes
     if (rc == -3) return fail(UMPA_HIP_E_NOMEM, "tiled path: device scratch allocation failed");
     if (rc != 0) return fail(UMPA_HIP_E_LAUNCH, "tiled path: launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
-    for (const auto& en : tt.entries) { TimedLaunch tl; tl.name = en.name; tl.t0 = en.t0; tl.t1 = en.t1; tl.fma = en.fma; tl.counts = en.counts; tl.fma_per = en.fma_per; m->launches.push_back(tl); }
     return 0;
 }
 

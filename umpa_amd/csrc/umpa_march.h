@@ -40,6 +40,8 @@
 
 namespace umpa {
 
+#define UMPA_MARCH_KMAX 42    // frames of a stack corr_march stages at most (march_plan's staging rule, umpa_tiled.h)
+
 struct MarchArgs {
     double* table;            // [strip][rows][(2ms-1)^2][tw]
     int tw;                   // columns of a table block (64, or WO where WO * 8 is a multiple of 128)
@@ -54,7 +56,7 @@ struct MarchArgs {
     int da, db;               // ring depths (rows): LA + 1, nuy + LA
     const char* baseA;        // byte address the A / B stack's frame offsets count from
     const char* baseB;
-    const unsigned* frame_off;   // [2][Na]: byte offset of frame k's image origin (position folded in) from baseA / baseB
+    unsigned frame_off[2 * UMPA_MARCH_KMAX];   // [2][Na]: byte offset of frame k's image origin (position folded in) from baseA / baseB
     int ablate;               // diagnostics: 1 no DMA, 2 no frame loop, 4 no filters, 8 no stores
     // which (strip, band, pass) units the launch computes (on-demand passes, umpa_ondemand.h: a unit = a "tile" lin = band *
     // nstrips + strip and a pass):
@@ -165,7 +167,7 @@ corr_march_kernel(ModelDev m, MarchArgs A, Sep1D sep)
             st = 1;
         }
         const int gc = min(max(col, A.bc0), A.bc1 - 1);
-        src_off[i] = gp(A.frame_off)[st * K + k] + (unsigned)gc * 8u;
+        src_off[i] = A.frame_off[st * K + k] + (unsigned)gc * 8u;
     }
     const bool dma = !(A.ablate & 1);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)A.baseA, (short)0, -1, 0x00020000);

@@ -493,14 +493,8 @@ replay_cost_kernel(ModelDev m, const double* table, size_t slot_stride, int drow
         live = live && xi >= row0 && xi < row0 + rows && xj < A.N1;
     } else {
         if (!first) break;
-        xj = blockIdx.x * 64 + threadIdx.x;
-        xi = blockIdx.y;
-        if (od.sub > 1) { xj = xj * od.sub + (od.sub >> 1); xi = xi * od.sub + (od.sub >> 1); }   // the sample lattice (od_run_chunk_lattice)
-        else {                                                          // a wave = a block of 16 x 4 pixels (as replay_walk, ReplayArgs::bw_log2)
-            xj = (blockIdx.x << 4) + (threadIdx.x & 15);
-            xi = (blockIdx.y << 2) + (threadIdx.x >> 4);
-        }
-        xi += row0;
+        xj = (blockIdx.x << 4) + (threadIdx.x & 15);                   // a wave = a block of 16 x 4 pixels (as replay_walk, ReplayArgs::bw_log2)
+        xi = (blockIdx.y << 2) + (threadIdx.x >> 4) + row0;
         live = xi < row0 + rows && xj < A.N1;
     }
     const size_t px = (size_t)xi * A.pitch + xj;                        // in the output arrays
@@ -531,7 +525,7 @@ replay_cost_kernel(ModelDev m, const double* table, size_t slot_stride, int drow
             walk_feed(w, memo, st, c, fit, m.call_cap);
         }
         if (L.miss) od_park(od, L, xi * A.N1 + xj);
-        else if (od.sub <= 1) {                                         // (the sample lattice's walks only predict: A.uv is read AND written)
+        else {
             double nb[16];
             walk_finish(w, memo, m.subpx, nb);
             store_pixel(A, px, KIND, w, memo, nb);

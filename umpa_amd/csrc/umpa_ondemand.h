@@ -28,7 +28,7 @@ namespace umpa {
 
 #define OD_SP 4                       // seed-tile spacing
 #define OD_ROUNDS 3                   // repair rounds; the last one computes everything that is still missing
-#define OD_SAMPLE_ROUNDS 3            // corr_march's schedule (od_run_chunk_march): rounds of the sample lattice
+#define OD_SAMPLE_ROUNDS 3            // corr_march's schedule (od_run_chunk_lattice): rounds of the sample lattice
 #define OD_STAGES 12                  // counter blocks of a chunk (>= OD_ROUNDS + 1 and >= OD_SAMPLE_ROUNDS + OD_ROUNDS + 3)
 // counters: int[8] per stage, stage 0 = steps 1-3, stage r = repair round r.
 #define OD_C_TILES  0                 // missed tiles listed by the replay of this stage
@@ -51,14 +51,13 @@ struct OdArgs {
                                       // (park on a miss), 3 persistent grid over px_in (park on a miss)
     int tc, ub, nbatch, npass, ntx, nty;   // pass / tile geometry of the table kernel
     int tr;                           // rows of a tile: 32 (corr_volume, corr_masked) or corr_march's band height (a tile = strip x band)
-    int sub;                          // replay mode 2: > 1 = only the pixels of a lattice, every sub-th in both directions (corr_march's
+    int sub;                          // replay_walk mode 2: > 1 = only the pixels of a lattice, every sub-th in both directions (corr_march's
                                       // sample stage); 0, 1: every pixel
     unsigned long long central;       // od_run_chunk_lattice: the passes every tile gets before any walk (those around shift (0, 0))
     int alone;                        // 1: a parked pixel asks for the pass it missed alone, 0: and for its neighbours in the row-offset direction
     int r0, c0;                       // seed tiles: ty % OD_SP == r0 and tx % OD_SP == c0
     int ub_inv;                       // ceil(2^16 / ub): x / ub = (x * ub_inv) >> 16 for 0 <= x < 70
     int nrow_inv;                     // the same for the row offsets per pass
-    int nearest;                      // prediction: 1 what the nearest seed tile visited, 0 the union over the (up to four) seed tiles around
 };
 
 // what the table kernels need of it (their SGPRs are nearly all taken by the window taps)
@@ -127,15 +126,11 @@ od_list_kernel(OdArgs od, int what)
     const int sy0 = ty - ((ty - od.r0) % OD_SP + OD_SP) % OD_SP, sx0 = tx - ((tx - od.c0) % OD_SP + OD_SP) % OD_SP;
     int best = 1 << 30;
     for (int a = 0; a < 2; a++)
-        for (int b = 0; b < 2; b++) {
+        for (int b = 0; b < 2; b++) {                                 // what the nearest of them visited
             const int sy = sy0 + a * OD_SP, sx = sx0 + b * OD_SP;
             if (sy < 0 || sy >= od.nty || sx < 0 || sx >= od.ntx) continue;
-            const unsigned long long v = gp(od.visited)[sy * od.ntx + sx];
-            if (!od.nearest) nd |= v;
-            else {
-                const int d = max(abs(sy - ty), abs(sx - tx)) * 8 + abs(sy - ty) + abs(sx - tx);
-                if (d < best) { best = d; nd = v; }
-            }
+            const int d = max(abs(sy - ty), abs(sx - tx)) * 8 + abs(sy - ty) + abs(sx - tx);
+            if (d < best) { best = d; nd = gp(od.visited)[sy * od.ntx + sx]; }
         }
     od_append(od, q, nd & all);
 }

@@ -543,9 +543,6 @@ struct TiledState {
     int ref_kind = -1, ref_K = 0;
     size_t ref_plane = 0;
     int ref_rect[4] = {0, 0, 0, 0};   // tiles (tx0, tx1, ty0, ty1) of the maps that were computed (PrepRect)
-    // corr_march (umpa_march.h): the frames' 32-bit byte offsets from the two stacks' base addresses, [2][K] on the device
-    unsigned* march_off = nullptr;  int march_off_cap = 0;
-    std::vector<unsigned> march_off_host;
     // on-demand passes (umpa_ondemand.h): device scratch, and page-locked slots the counters of a timed match land in
     void* od_buf = nullptr;   size_t od_cap = 0;
     int* od_host = nullptr;   int od_slot = 0;
@@ -555,15 +552,77 @@ struct TiledState {
 };
 #define UMPA_OD_SLOTS 256             // ring of counter slots (UMPA_OD_NCNT ints each) in TiledState::od_host
 
-// one entry per timed launch of a tiled match; the events come from the model's pool (`get`), so nothing is
-// created per launch and a match split into any number of row chunks is recorded completely
+// one timed launch; fma: FMAs of the launch; or, where that depends on what the device decided (on-demand passes), `fma_per`
+// per pass and `counts` -> the counters of the chunk, copied to page-locked memory behind its last kernel (counts[OD_C_DONE] =
+// passes computed)
+struct TimedLaunch { int name; hipEvent_t t0, t1; double fma; const int* counts; double fma_per; };
+
+// Brackets the launches of a tiled match with events, recorded straight into the model's list (`out`; null: timing off).  The
+// events come from the model's pool (`get`), so nothing is created per launch and a match split into any number of row chunks
+// is recorded completely.
 struct TiledTimers {
-    // fma: FMAs of the launch; or, where that depends on what the device decided (on-demand passes), `fma_per` per pass and
-    // `counts` -> the counters of the chunk, copied to page-locked memory behind its last kernel (counts[OD_C_DONE] = passes computed)
-    struct Entry { int name; hipEvent_t t0, t1; double fma; const int* counts; double fma_per; };
-    std::vector<Entry> entries;
+    std::vector<TimedLaunch>* out;
     std::function<hipEvent_t()> get;
+    hipStream_t s;
+    size_t first;                     // this match's first entry
+    bool open = false;
+    TiledTimers(std::vector<TimedLaunch>* out_, std::function<hipEvent_t()> get_, hipStream_t s_)
+        : out(out_), get(std::move(get_)), s(s_), first(out_ ? out_->size() : 0) {}
+    void tic(int name)
+    {
+        open = false;
+        if (!out) return;
+        TimedLaunch en = {name, get(), get(), 0.0, nullptr, 0.0};
+        if (!en.t0 || !en.t1) return;
+        (void)hipEventRecord(en.t0, s);
+        out->push_back(en);
+        open = true;
+    }
+    void toc(double fma = 0.0)
+    {
+        if (!open) return;
+        out->back().fma = fma;
+        (void)hipEventRecord(out->back().t1, s);
+        open = false;
+    }
+    // an on-demand chunk: all its FMAs on the last launch of table kernel `name`
+    void attach(int name, const int* counts, double fma_per)
+    {
+        if (out) for (size_t i = out->size(); i-- > first;)
+            if ((*out)[i].name == name) { (*out)[i].counts = counts; (*out)[i].fma_per = fma_per; break; }
+    }
 };
+
+// The tiled path's switches, read once at the start of a match, not cached: the tests switch them between
+// matches.
+struct TiledEnv {
+    int ondemand;             // UMPA_HIP_ONDEMAND: -1 unset, 0, 1, 2 = another value (od_enabled; corr_march's stages: any but 0)
+    bool march;               // UMPA_HIP_MARCH: corr_march where it is instantiated (default), 0 never
+    int march_od_rows;        // UMPA_HIP_MARCH_OD_ROWS: band height of corr_march's on-demand units
+    size_t table_bytes;       // UMPA_HIP_TABLE_MB: the shift table's budget
+    int corr_shape;           // UMPA_HIP_CORR_SHAPE: corr_volume's workgroup shape by number (launch_corr_shape), 0 automatic
+    int ablate, ablate_replay, ablate_march, ablate_masked;   // UMPA_HIP_ABLATE(_REPLAY, _MARCH, _MASKED): the kernels' `ablate`
+    bool od_debug;            // UMPA_HIP_OD_DEBUG: corr_march's on-demand counters on stderr (a host wait)
+};
+
+inline TiledEnv tiled_env()
+{
+    auto num = [](const char* name, long fallback) { const char* e = getenv(name); return e ? atol(e) : fallback; };
+    TiledEnv E;
+    const char* od = getenv("UMPA_HIP_ONDEMAND");
+    E.ondemand = !od ? -1 : atoi(od) == 0 ? 0 : atoi(od) == 1 ? 1 : 2;
+    E.march = num("UMPA_HIP_MARCH", 1) != 0;
+    E.march_od_rows = (int)std::max(32L, num("UMPA_HIP_MARCH_OD_ROWS", 512));
+    // 288 GB of HBM: C3's 30 GB table in two chunks (4 GiB: 50.2 -> 49.3 ms)
+    E.table_bytes = (size_t)std::max(16L, num("UMPA_HIP_TABLE_MB", 16384)) << 20;
+    E.corr_shape = (int)num("UMPA_HIP_CORR_SHAPE", 0);
+    E.ablate = (int)num("UMPA_HIP_ABLATE", 0);
+    E.ablate_replay = (int)num("UMPA_HIP_ABLATE_REPLAY", 0);
+    E.ablate_march = (int)num("UMPA_HIP_ABLATE_MARCH", 0);
+    E.ablate_masked = (int)num("UMPA_HIP_ABLATE_MASKED", 0);
+    E.od_debug = getenv("UMPA_HIP_OD_DEBUG") != nullptr;
+    return E;
+}
 
 inline bool tiled_supported(int Nw, int ms, int Na)
 {
@@ -596,8 +655,6 @@ inline void tiled_release(TiledState& st)
     if (st.table) (void)hipFree(st.table);
     if (st.od_buf) (void)hipFree(st.od_buf);
     if (st.od_host) (void)hipHostFree(st.od_host);
-    if (st.march_off) (void)hipFree(st.march_off);
-    st.march_off = nullptr; st.march_off_cap = 0; st.march_off_host.clear();
     st.maps = st.table = nullptr;
     st.od_buf = nullptr; st.od_host = nullptr; st.od_cap = 0;
     st.maps_cap = st.table_cap = 0;
@@ -616,17 +673,25 @@ inline int pick_ub(int UJ)
     return best;
 }
 
-inline int tiled_corr_shape()
+inline int current_device()
 {
-    const char* e = getenv("UMPA_HIP_CORR_SHAPE");                    // tuning override, see launch_corr_shape; 0 = automatic
-    return e ? atoi(e) : 0;
+    int devid = 0;
+    (void)hipGetDevice(&devid);
+    return devid;
 }
 
-// serialises the one-time per-device kernel attribute calls (two host threads may match on one model type)
-inline std::mutex& tiled_attr_mutex()
+// Raises KERNEL's dynamic-LDS limit to `bytes`, once per device (the attribute is per device; the lock: two host threads
+// may match on one model type).
+template <auto KERNEL>
+inline hipError_t set_lds_limit_once(int bytes, int devid)
 {
     static std::mutex mu;
-    return mu;
+    static bool done[64] = {};
+    std::lock_guard<std::mutex> lock(mu);
+    if (done[devid & 63]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) done[devid & 63] = true;
+    return e;
 }
 
 inline OdCorr od_corr_args(const OdArgs& od)
@@ -643,6 +708,7 @@ inline OdCorr od_corr_args(const OdArgs& od)
 struct CorrLaunch {
     OdArgs od;                // od.mode 0: every pass (static grid); 3: seed tiles (compact static grid); 2: queue over od.items
     bool dry;                 // only report the geometry
+    int shape;                // UMPA_HIP_CORR_SHAPE (launch_corr_shape): 0 automatic
     int tc, ub, nrow, nbatch, npass, ntx, nty;   // out: tile columns, column / row offsets per pass, ... of the shape that was picked
     double fma_per_pass;      // out: fp64 FMAs one (tile, pass) executes (roofline accounting)
 };
@@ -673,30 +739,13 @@ inline hipError_t launch_corr(const ModelDev& dev, CorrArgs A, const Sep1D& sep,
     L.fma_per_pass = (double)C::QR * C::NQB * C::QB * UB * C::NROW * dev.Na +
                      (double)C::NPL * C::QR * TC * C::S + (double)C::NPL * C::TR * TC * C::S;
     if (L.dry) return hipSuccess;
-    static bool attr_set[64] = {};                                    // the attribute is per device
-    int devid = 0;
-    (void)hipGetDevice(&devid);
-    {
-        std::lock_guard<std::mutex> lock(tiled_attr_mutex());
-        if (!attr_set[devid & 63]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_volume_kernel<NW, UB, TC, NTG, UI, WPC, NF, RO>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS);
-            if (e != hipSuccess) return e;
-            attr_set[devid & 63] = true;
-        }
-    }
+    const int devid = current_device();
+    hipError_t e = set_lds_limit_once<&corr_volume_kernel<NW, UB, TC, NTG, UI, WPC, NF, RO>>((int)C::LDS, devid);
+    if (e != hipSuccess) return e;
     const OdCorr oc = od_corr_args(L.od);
     if (L.od.mode == 2) {                                             // persistent grid over the work list: one workgroup per slot of the chip
-        static bool qattr_set[64] = {};
-        {
-            std::lock_guard<std::mutex> lock(tiled_attr_mutex());
-            if (!qattr_set[devid & 63]) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_volume_queue_kernel<NW, UB, TC, NTG, UI, WPC, NF, RO>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS);
-                if (e != hipSuccess) return e;
-                qattr_set[devid & 63] = true;
-            }
-        }
+        e = set_lds_limit_once<&corr_volume_queue_kernel<NW, UB, TC, NTG, UI, WPC, NF, RO>>((int)C::LDS, devid);
+        if (e != hipSuccess) return e;
         const int grid = ((device_cu_count() * WPC + 7) / 8) * 8;
         hipLaunchKernelGGL((corr_volume_queue_kernel<NW, UB, TC, NTG, UI, WPC, NF, RO>), dim3(grid), dim3(C::NT), C::LDS, s, dev, A, sep, oc);
     } else {
@@ -734,7 +783,7 @@ inline hipError_t launch_corr(const ModelDev& dev, CorrArgs A, const Sep1D& sep,
 template <int NW, int UB>
 inline hipError_t launch_corr_shape(const ModelDev& dev, const CorrArgs& A, const Sep1D& sep, hipStream_t s, CorrLaunch& L)
 {
-    const int want = tiled_corr_shape();
+    const int want = L.shape;
     // three row offsets per pass: enough frames for the staging it saves to outweigh its longer flush (5 frames, C5: 3.87
     // against 3.80 ms per projection with the two-per-CU shape).  An idle third of the last pass (2 max_shift - 1 not a
     // multiple of three) costs less than it saves (tools/shape_rate.py, C2's stack, shape 1 -> 5: max_shift 3: 0.69 -> 0.60 ms,
@@ -794,12 +843,13 @@ struct MarchPlan {
 #define UMPA_MARCH_NPT 4
 #define UMPA_MARCH_LA 2
 
-inline bool march_wanted(int Nw)
-{
-    const char* e = getenv("UMPA_HIP_MARCH");                         // 0: never, 1: wherever it is instantiated (Nw 6, 7)
-    if (e) return atoi(e) != 0 && (Nw == 6 || Nw == 7);
-    return Nw == 6 || Nw == 7;
-}
+// LDS-DMA instructions per step for K frames: A pieces, B pieces (nbe entries per B array); a plan needs them to fit the
+// offsets the waves hold (UMPA_MARCH_NPT per wave)
+constexpr int march_staging(int K, int nbe) { return (K + 1) / 2 + (K * 2 * nbe + 63) / 64; }
+constexpr bool march_staging_fits(int K, int nbe) { return march_staging(K, nbe) <= UMPA_MARCH_NPT * (UMPA_MARCH_NT / 64); }
+// the most frames any plan stages (nbe = 20, NXB = 4, is the smallest B array): MarchArgs::frame_off holds that many
+static_assert(march_staging_fits(UMPA_MARCH_KMAX, 20) && !march_staging_fits(UMPA_MARCH_KMAX + 1, 20),
+              "UMPA_MARCH_KMAX must be the largest frame count march_plan accepts");
 
 inline MarchPlan march_plan(int Nw, int UJ, int K, int N1d)
 {
@@ -814,7 +864,7 @@ inline MarchPlan march_plan(int Nw, int UJ, int K, int N1d)
     P.nt = UMPA_MARCH_NT;
     P.npa = (K + 1) / 2;
     P.npb = (K * 2 * nbe + 63) / 64;
-    if (P.npa + P.npb > UMPA_MARCH_NPT * (P.nt / 64)) return P;       // more staging instructions per step than the waves hold offsets for
+    if (!march_staging_fits(K, nbe)) return P;                        // more staging instructions per step than the waves hold offsets for
     P.a_slot = (unsigned)P.npa * 1024u;
     P.b_slot = (unsigned)P.npb * 1024u;
     for (int nuy = std::min(UJ, (P.nt / 16) / UJ); nuy >= 1; nuy--) {  // as many row offsets per pass as the waves and the LDS hold
@@ -828,12 +878,10 @@ inline MarchPlan march_plan(int Nw, int UJ, int K, int N1d)
     return P;
 }
 
-// the frames' byte offsets from the lowest frame address of each stack (positions folded in): false if a stack does not fit
-// 32-bit offsets up to the last image row the kernel may address
-inline bool march_offsets(const FrameDesc* hf, int K, int sigma, const FrameBox& box, std::vector<unsigned>& off,
-                          const char*& baseA, const char*& baseB)
+// the frames' byte offsets from the lowest frame address of each stack (positions folded in) into A.frame_off, the bases
+// into A.baseA / baseB: false if a stack does not fit 32-bit offsets up to the last image row the kernel may address
+inline bool march_offsets(const FrameDesc* hf, int K, int sigma, const FrameBox& box, MarchArgs& A)
 {
-    off.assign(2 * (size_t)K, 0u);
     for (int st = 0; st < 2; st++) {
         const bool sam = (st == 0) == (sigma > 0);                    // A = the stack whose window does not move (umpa_corr.h)
         intptr_t lo = INTPTR_MAX, hi = INTPTR_MIN;
@@ -844,8 +892,8 @@ inline bool march_offsets(const FrameDesc* hf, int K, int sigma, const FrameBox&
         const uint64_t span = (uint64_t)(hi - lo) + ((uint64_t)box.r1 + 2) * (uint64_t)box.Wf * 8u;
         if (span >= ((uint64_t)1 << 32) - 4096) return false;
         for (int k = 0; k < K; k++)
-            off[(size_t)st * K + k] = (unsigned)((intptr_t)(sam ? hf[k].sam : hf[k].ref) - ((intptr_t)hf[k].pi * box.Wf + hf[k].pj) * 8 - lo);
-        (st == 0 ? baseA : baseB) = (const char*)lo;
+            A.frame_off[st * K + k] = (unsigned)((intptr_t)(sam ? hf[k].sam : hf[k].ref) - ((intptr_t)hf[k].pi * box.Wf + hf[k].pj) * 8 - lo);
+        (st == 0 ? A.baseA : A.baseB) = (const char*)lo;
     }
     return true;
 }
@@ -853,18 +901,9 @@ inline bool march_offsets(const FrameDesc* hf, int K, int sigma, const FrameBox&
 template <int NW, int NXB>
 inline hipError_t launch_march_inst(const ModelDev& dev, const MarchArgs& A, const Sep1D& sep, const MarchPlan& P, hipStream_t s)
 {
-    auto kern = corr_march_kernel<NW, NXB, UMPA_MARCH_NPT, UMPA_MARCH_LA, UMPA_MARCH_NT, 3>;
-    static bool attr_set[64] = {};
-    int devid = 0;
-    (void)hipGetDevice(&devid);
-    {
-        std::lock_guard<std::mutex> lock(tiled_attr_mutex());
-        if (!attr_set[devid & 63]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, UMPA_LDS_BUDGET);
-            if (e != hipSuccess) return e;
-            attr_set[devid & 63] = true;
-        }
-    }
+    constexpr auto kern = &corr_march_kernel<NW, NXB, UMPA_MARCH_NPT, UMPA_MARCH_LA, UMPA_MARCH_NT, 3>;
+    const hipError_t e = set_lds_limit_once<kern>(UMPA_LDS_BUDGET, current_device());
+    if (e != hipSuccess) return e;
     const int nitems = A.nstrips * A.nbands;
     // (work list: a slot for every unit there could be; the workgroups past the list's end leave at once)
     const int grid = A.items ? 8 * ((nitems * A.npass + 7) / 8) : 8 * ((nitems + 7) / 8) * A.npass;
@@ -898,7 +937,6 @@ inline hipError_t launch_march(const ModelDev& dev, MarchArgs A, const Sep1D& se
         const double cost = rounds * (std::ceil((double)A.rows / nb) + 2 * Nw + 8);
         if (cost < best_cost - 1e-9) { best_cost = cost; best_nb = nb; }
     }
-    { const char* e = getenv("UMPA_HIP_MARCH_BANDS"); if (e && atoi(e) > 0) best_nb = atoi(e); }
     if (A.nbands <= 0) { A.nbands = best_nb; A.band_rows = (A.rows + best_nb - 1) / best_nb; }   // (on-demand passes: the bands are the caller's tiles)
     if (fma) march_fma(dev, A, fma);
     if (Nw == 6) return P.nxb == 4 ? launch_march_inst<6, 4>(dev, A, sep, P, s) : launch_march_inst<6, 8>(dev, A, sep, P, s);
@@ -926,18 +964,8 @@ template <int KIND, int NW>
 inline hipError_t launch_prep(const ModelDev& dev, const Maps& M, const Sep1D& sep, int sides, hipStream_t s, const PrepRect& PR)
 {
     using C = PrepCfg<NW>;
-    static bool attr_set[64] = {};                                    // the attribute is per device
-    int devid = 0;
-    (void)hipGetDevice(&devid);
-    {
-        std::lock_guard<std::mutex> lock(tiled_attr_mutex());
-        if (!attr_set[devid & 63]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_maps_kernel<KIND, NW>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS);
-            if (e != hipSuccess) return e;
-            attr_set[devid & 63] = true;
-        }
-    }
+    const hipError_t e = set_lds_limit_once<&prep_maps_kernel<KIND, NW>>((int)C::LDS, current_device());
+    if (e != hipSuccess) return e;
     const int ntx = PR.tx1 - PR.tx0, nty = PR.ty1 - PR.ty0;
     const int total = ntx * nty, grid = ((total + 7) / 8) * 8;
     if (total > 0) hipLaunchKernelGGL((prep_maps_kernel<KIND, NW>), dim3(grid), dim3(C::NT), C::LDS, s, dev, M, sep, ntx, nty, sides, PR.tx0, PR.ty0);
@@ -966,12 +994,11 @@ inline hipError_t launch_prep(const ModelDev& dev, const Maps& M, const Sep1D& s
 // dark-field C2 + mask 41.8 -> 25.2 ms, plain 11.5 -> 8.2 ms -- leaving out ~40 % of the passes pays; on the plain
 // path the serial small launches (seed tiles, repair rounds: ~0.5 ms on C2, ~7 ms on C3) cost what the table kernel
 // saves (C2 3.44 -> 3.46 ms, C3 48.0 -> 46.7 ms), so it is off there unless UMPA_HIP_ONDEMAND=1 asks for it.
-inline bool od_enabled(int ntiles, int npass, bool masked)
+inline bool od_enabled(const TiledEnv& E, int ntiles, int npass, bool masked)
 {
-    const char* e = getenv("UMPA_HIP_ONDEMAND");                      // 0: never, 1: whenever a tile has 2..64 passes (read per match: the tests switch it)
     if (npass > 64 || npass < 2) return false;
-    if (e && atoi(e) == 0) return false;
-    if (e && atoi(e) == 1) return ntiles >= 2;
+    if (E.ondemand == 0) return false;                                // 0: never, 1: whenever a tile has 2..64 passes
+    if (E.ondemand == 1) return ntiles >= 2;
     return masked && ntiles >= 6;                                     // a few tiles at least: one of them is a seed tile
 }
 
@@ -1015,7 +1042,6 @@ inline hipError_t od_run_chunk(OdArgs od, const OdBuffers& B, hipStream_t s, Cor
     if (e != hipSuccess) return e;
     const int ntiles = od.ntx * od.nty, lb = (ntiles + 255) / 256;
     od.r0 = std::min(1, od.nty - 1); od.c0 = std::min(1, od.ntx - 1);
-    { const char* pe = getenv("UMPA_HIP_OD_PRED"); od.nearest = pe && pe[0] == '0' ? 0 : 1; }   // tuning: 0 = union over the seed tiles around
     auto stage = [&](int r) { return B.counters + 8 * r; };
     // 1. seed tiles: every pass (a compact grid over them); their pixels record what they read
     od.cnt_in = nullptr; od.cnt_out = stage(0);
@@ -1041,24 +1067,24 @@ inline hipError_t od_run_chunk(OdArgs od, const OdBuffers& B, hipStream_t s, Cor
     return hipSuccess;
 }
 
-// The same without seed tiles: every walk starts at shift (0, 0), so the prediction can be the walks themselves on a lattice of
-// sample pixels.  For every table kernel; corr_march's unit of work is (strip, band, pass) -- a "tile" is a strip x band, a pass
-// NUY row offsets x every column offset.
+// The same without seed tiles, for corr_march, whose unit of work is (strip, band, pass) -- a "tile" is a strip x band, a pass
+// NUY row offsets x every column offset: every walk starts at shift (0, 0), so the prediction can be the walks themselves on a
+// lattice of sample pixels.  (Under corr_volume / corr_masked the seed tiles predict their 32 x 32 tiles better: DESIGN.md.)
 //   0. the passes around shift (0, 0) (od.central), every tile;
-//   1. the pixels of a lattice (every `sub`-th in both directions) walk; one that needs a pass that is not there parks and asks
+//   1. the pixels of a lattice (every OD_LATTICE_SUB-th in both directions) walk; one that needs a pass that is not there parks and asks
 //      for it (od_park); OD_SAMPLE_ROUNDS rounds of  list -> table kernel over the list -> parked pixels again,  then what
-//      the last round still asked for.  Their cost is 1 / sub^2 of a replay each; what they leave behind is `done`;
+//      the last round still asked for.  Their cost is 1 / OD_LATTICE_SUB^2 of a replay each; what they leave behind is `done`;
 //      (these walks store nothing: the start shifts A.uv are read AND written by a walk that ends);
-//   2. every pixel walks (the lattice's again: they are 1 / sub^2 of the pixels); OD_ROUNDS repair rounds as in od_run_chunk,
+//   2. every pixel walks (the lattice's again: they are 1 / OD_LATTICE_SUB^2 of the pixels); OD_ROUNDS repair rounds as in od_run_chunk,
 //      the last one computing every pass the tiles with parked pixels lack.
+#define OD_LATTICE_SUB 8
 template <class Corr, class Replay>
-inline hipError_t od_run_chunk_lattice(OdArgs od, const OdBuffers& B, hipStream_t s, Corr corr, Replay replay, int sub)
+inline hipError_t od_run_chunk_lattice(OdArgs od, const OdBuffers& B, hipStream_t s, Corr corr, Replay replay)
 {
     hipError_t e = hipMemsetAsync(od.done, 0, B.zero_bytes, s);
     if (e != hipSuccess) return e;
     const int ntiles = od.ntx * od.nty, lb = (ntiles + 255) / 256;
     od.r0 = od.c0 = -1;                                               // no seed tiles
-    od.nearest = 1;
     auto stage = [&](int r) { return B.counters + 8 * r; };
     int k = 0;                                                        // the stage whose counters were written last
     auto round = [&](int what, bool walk) {
@@ -1078,15 +1104,13 @@ inline hipError_t od_run_chunk_lattice(OdArgs od, const OdBuffers& B, hipStream_
     hipLaunchKernelGGL(od_list_kernel, dim3(lb), dim3(256), 0, s, od, 4);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     od.mode = 2; if ((e = corr(od)) != hipSuccess) return e;
-    if (sub > 1) {
-        od.sub = sub; od.mode = 2; if ((e = replay(od)) != hipSuccess) return e;
-        for (int r = 1; r <= OD_SAMPLE_ROUNDS; r++) if ((e = round(2, true)) != hipSuccess) return e;
-        if ((e = round(2, false)) != hipSuccess) return e;            // (also clears the flags and requests of the last round's tiles)
-        od.sub = 0;
-        k++;                                                          // a fresh stage for the walks of every pixel
-        od.cnt_in = nullptr; od.cnt_out = stage(k);
-        od.tile_in = nullptr; od.tile_out = B.tiles[k & 1]; od.px_in = nullptr; od.px_out = B.px[k & 1];
-    }
+    od.sub = OD_LATTICE_SUB; od.mode = 2; if ((e = replay(od)) != hipSuccess) return e;
+    for (int r = 1; r <= OD_SAMPLE_ROUNDS; r++) if ((e = round(2, true)) != hipSuccess) return e;
+    if ((e = round(2, false)) != hipSuccess) return e;                // (also clears the flags and requests of the last round's tiles)
+    od.sub = 0;
+    k++;                                                              // a fresh stage for the walks of every pixel
+    od.cnt_in = nullptr; od.cnt_out = stage(k);
+    od.tile_in = nullptr; od.tile_out = B.tiles[k & 1]; od.px_in = nullptr; od.px_out = B.px[k & 1];
     od.mode = 2; if ((e = replay(od)) != hipSuccess) return e;
     for (int r = 1; r <= OD_ROUNDS; r++) if ((e = round(r == OD_ROUNDS ? 3 : 2, true)) != hipSuccess) return e;
     return hipSuccess;
@@ -1107,44 +1131,11 @@ inline unsigned long long od_central_passes(int ms, int sigma, int nrow, int nba
     return mask;
 }
 
-// which prediction the on-demand stages of corr_volume / corr_masked use: UMPA_HIP_OD_PRED = lattice | seed (default) | 0 (seed,
-// union over the seed tiles around); corr_march's is always the lattice
-inline bool od_lattice_wanted()
-{
-    const char* e = getenv("UMPA_HIP_OD_PRED");
-    return e && e[0] == 'l';                                          // (measured: the seed tiles predict corr_volume's and corr_masked's 32 x 32 tiles better)
-}
-inline int od_alone_wanted()                                         // 1: parked pixels ask for the missed pass alone (od_park)
-{
-    const char* e = getenv("UMPA_HIP_OD_ALONE");
-    return e ? atoi(e) : 1;
-}
-inline int od_lattice_sub(int fallback)
-{
-    const char* e = getenv("UMPA_HIP_OD_SUB");
-    return e ? atoi(e) : fallback;
-}
+// ---- what a match on the plain and on the masked path share
 
-inline size_t tiled_table_budget()
+// The map planes of a match (SamSq, RefSq and, DF, the per-frame WS and MR) and M's geometry.  0 or -3.
+inline int tiled_maps(TiledState& st, Maps& M, int kind, int K, int H, int W, const FrameBox& box)
 {
-    const char* e = getenv("UMPA_HIP_TABLE_MB");
-    long mb = e ? atol(e) : 16384;                                    // 288 GB of HBM: C3's 30 GB table in two chunks (4 GiB: 50.2 -> 49.3 ms)
-    if (mb < 16) mb = 16;
-    return (size_t)mb << 20;
-}
-
-// One match of a region on the tiled path.  Returns 0, -3 (allocation) or a positive hipError_t.
-// `reuse_ref_maps`: the caller vouches that the reference frames are those of the previous call (it owns them).
-// `piece_rows` > 0: row chunks of at most that many dense rows (a multiple of 32) even where the table budget would
-// allow more (the host-array entry point downloads the rows of chunk c while chunk c+1 is being matched, the multi-GPU
-// leg sends them to rank 0); `on_rows(xi_lo, xi_hi)` is called after the kernels of a chunk have been enqueued.
-
-inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int W, const FrameBox& box, const RegionArgs& A,
-                       hipStream_t s, TiledTimers* tt, bool reuse_ref_maps,
-                       int piece_rows = 0, const std::function<void(int, int)>& on_rows = nullptr,
-                       const FrameDesc* host_frames = nullptr)      // a host copy of dev.frames (corr_march's staging offsets)
-{
-    const int K = dev.Na, Nw = dev.Nw, ms = dev.ms, UJ = 2 * ms - 1;
     const size_t plane = (size_t)H * W;
     const size_t KP = ((size_t)K + 1) / 2;                             // pair planes per stack (Maps)
     const size_t nmaps = kind == 1 ? 2 + 4 * KP : 2;
@@ -1156,178 +1147,240 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
         st.maps_cap = nmaps * plane;
     }
     if (st.ref_kind != kind || st.ref_K != K || st.ref_plane != plane) st.ref_maps_ok = false;
-    Maps M;
     M.H = H; M.W = W;
     M.br0 = box.r0; M.br1 = box.r1; M.bc0 = box.c0; M.bc1 = box.c1; M.Wf = box.Wf;
     M.SamSq = st.maps; M.RefSq = st.maps + plane;
     M.WS = kind == 1 ? st.maps + 2 * plane : nullptr;
     M.MR = kind == 1 ? st.maps + (2 + 2 * KP) * plane : nullptr;
+    return 0;
+}
 
-    // The table lives on the dense (unit-step) grid under the region: with step > 1 every step-th entry is used
-    // (tiled_applicable only sends small steps here).  Rows per chunk: the shift table of one chunk stays within
-    // the budget (whole tiles).
-    const int N0d = A.step0 * (A.N0 - 1) + 1, N1d = A.step1 * (A.N1 - 1) + 1;
-    // table rows are padded to whole 256-byte tile rows: every (tile, row) of a plane is then a run of whole, aligned
-    // 128-byte lines (C2: 2028 -> 2048 doubles; UMPA_HIP_TABLE_ALIGN=1 packs the rows as round 3 did)
-    static const int table_align = getenv("UMPA_HIP_TABLE_ALIGN") ? std::max(1, atoi(getenv("UMPA_HIP_TABLE_ALIGN"))) : 32;
-    int N1p = (N1d + table_align - 1) / table_align * table_align;
-    // wide windows: the table comes from corr_march (strip-blocked: [strip][rows][shift][tw], one "row" = nstrips * UJ^2 * tw doubles)
-    MarchPlan MP;
-    memset(&MP, 0, sizeof(MP));
-    const char* march_baseA = nullptr; const char* march_baseB = nullptr;
-    {
-        if (host_frames && march_wanted(Nw)) {
-            MP = march_plan(Nw, UJ, K, N1d);
-            if (MP.ok && !march_offsets(host_frames, K, dev.ref_mode ? -1 : 1, box, st.march_off_host, march_baseA, march_baseB)) MP.ok = false;
-        }
-    }
-    if (MP.ok) N1p = MP.nstrips * MP.tw;                               // doubles per dense row and shift
-    // on-demand passes of corr_march (od_run_chunk_march): UMPA_HIP_ONDEMAND=1 on, =0 off
-    bool march_od = false;
-    { const char* od_env = getenv("UMPA_HIP_ONDEMAND"); if (od_env) march_od = atoi(od_env) != 0; }
-    march_od = march_od && MP.ok && MP.npass >= 3 && MP.npass <= 64 && !getenv("UMPA_HIP_ABLATE_MARCH");
-    const size_t row_bytes = (size_t)UJ * UJ * N1p * sizeof(double);
-    long rows_chunk = (long)(tiled_table_budget() / row_bytes) / UMPA_TILE * UMPA_TILE;
+// Dense rows per chunk of the table (whole tiles) and the table itself: as many rows of `per_row` doubles as the budget
+// holds, at most `piece_rows` (> 0) and at most what fits the table an earlier allocation left us; the allocation halves
+// the chunk until it succeeds (a card with less free memory than the budget assumes: smaller chunks rather than no tiled
+// path).  slot_pitch > 0: a table slot (rows_chunk * slot_pitch doubles) is addressed with a 32-bit stride (eval_lookup).
+// Returns 0, -3 or a positive hipError_t.
+inline int tiled_table(TiledState& st, const TiledEnv& E, size_t per_row, int N0d, int piece_rows, size_t slot_pitch, long& rows_chunk)
+{
+    rows_chunk = (long)(E.table_bytes / (per_row * sizeof(double))) / UMPA_TILE * UMPA_TILE;
     if (rows_chunk < UMPA_TILE) rows_chunk = UMPA_TILE;
     if (rows_chunk > N0d) rows_chunk = ((long)N0d + UMPA_TILE - 1) / UMPA_TILE * UMPA_TILE;
     if (piece_rows > 0) {
         const long want = ((long)piece_rows + UMPA_TILE - 1) / UMPA_TILE * UMPA_TILE;
         if (want < rows_chunk) rows_chunk = want;
     }
-    {   // eval_lookup multiplies the slot number by a 32-bit slot stride (rows_chunk * N1d)
-        const long cap = (long)(0xffffffffull / (size_t)N1p) / UMPA_TILE * UMPA_TILE;
+    if (slot_pitch > 0) {
+        const long cap = (long)(0xffffffffull / slot_pitch) / UMPA_TILE * UMPA_TILE;
         if (cap < UMPA_TILE) return (int)hipErrorInvalidValue;
         if (rows_chunk > cap) rows_chunk = cap;
     }
     if (st.table_limited && st.table_cap > 0) {                        // an earlier allocation of the full budget failed: live with what we got
-        const long fit = (long)(st.table_cap / ((size_t)UJ * UJ * N1p)) / UMPA_TILE * UMPA_TILE;
+        const long fit = (long)(st.table_cap / per_row) / UMPA_TILE * UMPA_TILE;
         if (fit >= UMPA_TILE && fit < rows_chunk) rows_chunk = fit;
     }
-    size_t table_need = (size_t)UJ * UJ * rows_chunk * N1p;
-    if (st.table_cap < table_need) {
+    size_t need = per_row * rows_chunk;
+    if (st.table_cap < need) {
         if (st.table) (void)hipFree(st.table);
         st.table = nullptr; st.table_cap = 0;
-        // a card with less free memory than the budget assumes: smaller row chunks rather than no tiled path
-        while (hipMalloc((void**)&st.table, table_need * sizeof(double)) != hipSuccess) {
+        while (hipMalloc((void**)&st.table, need * sizeof(double)) != hipSuccess) {
             (void)hipGetLastError();
             st.table = nullptr;
             if (rows_chunk <= UMPA_TILE) return -3;
             st.table_limited = true;
             rows_chunk = std::max<long>(UMPA_TILE, rows_chunk / 2 / UMPA_TILE * UMPA_TILE);
-            table_need = (size_t)UJ * UJ * rows_chunk * N1p;
+            need = per_row * rows_chunk;
         }
-        st.table_cap = table_need;
+        st.table_cap = need;
     }
+    return 0;
+}
 
-    bool timing_open = false;
-    auto tic = [&](int name) {
-        timing_open = false;
-        if (!tt) return;
-        TiledTimers::Entry en = {name, tt->get(), tt->get(), 0.0, nullptr, 0.0};
-        if (!en.t0 || !en.t1) return;
-        (void)hipEventRecord(en.t0, s);
-        tt->entries.push_back(en);
-        timing_open = true;
-    };
-    auto toc = [&](double fma = 0.0) {
-        if (!timing_open) return;
-        tt->entries.back().fma = fma;
-        (void)hipEventRecord(tt->entries.back().t1, s);
-        timing_open = false;
-    };
-
-    hipError_t e = hipErrorInvalidValue;
-    tic(2);
-    PrepRect PRc = {0, 0, 0, 0};
-    UMPA_NW_SWITCH(Nw, (PRc = prep_rect<NWC>(M, A, ms)))
-    const bool covered = st.ref_rect[0] <= PRc.tx0 && st.ref_rect[1] >= PRc.tx1 && st.ref_rect[2] <= PRc.ty0 && st.ref_rect[3] >= PRc.ty1;
-    const int sides = (reuse_ref_maps && st.ref_maps_ok && covered) ? 1 : 3;
+// The maps of the tiles the region reads (prep_rect): both sides (3), or `reuse_sides` where the caller vouches for the
+// reference frames (`reuse`) and the reference-side maps cover those tiles -- 1, the sample side (plain path), or 0, nothing
+// (masked path: only the reference means are read).
+inline hipError_t tiled_prep(TiledState& st, const ModelDev& dev, const Maps& M, const RegionArgs& A, int kind, bool reuse,
+                             int reuse_sides, hipStream_t s, TiledTimers& tt)
+{
+    PrepRect PR = {0, 0, 0, 0};
+    UMPA_NW_SWITCH(dev.Nw, (PR = prep_rect<NWC>(M, A, dev.ms)))
+    const bool covered = st.ref_rect[0] <= PR.tx0 && st.ref_rect[1] >= PR.tx1 && st.ref_rect[2] <= PR.ty0 && st.ref_rect[3] >= PR.ty1;
+    const int sides = (reuse && st.ref_maps_ok && covered) ? reuse_sides : 3;
     st.ref_maps_ok = false;
-    if (kind == 1) { UMPA_NW_SWITCH(Nw, (e = launch_prep<1, NWC>(dev, M, st.sep, sides, s, PRc))) }
-    else { UMPA_NW_SWITCH(Nw, (e = launch_prep<0, NWC>(dev, M, st.sep, sides, s, PRc))) }
-    toc();
-    if (e != hipSuccess) return (int)e;
-    st.ref_maps_ok = true; st.ref_kind = kind; st.ref_K = K; st.ref_plane = plane;
-    st.ref_rect[0] = PRc.tx0; st.ref_rect[1] = PRc.tx1; st.ref_rect[2] = PRc.ty0; st.ref_rect[3] = PRc.ty1;
-
-    int ub = pick_ub(UJ);
-    { const char* e = getenv("UMPA_HIP_UB"); if (e) ub = atoi(e); }      // tuning override: 9, 8, 7 or 5
-    st.stat_n = 0; st.stat_total_passes = 0.0;
-    if (MP.ok) {                                                       // the frames' staging offsets (stable storage: the state's own vector)
-        if (st.march_off_cap < 2 * K) {
-            if (st.march_off) (void)hipFree(st.march_off);
-            st.march_off = nullptr; st.march_off_cap = 0;
-            if (hipMalloc((void**)&st.march_off, 2 * (size_t)K * sizeof(unsigned)) != hipSuccess) return -3;
-            st.march_off_cap = 2 * K;
-        }
-        if ((e = hipMemcpyAsync(st.march_off, st.march_off_host.data(), 2 * (size_t)K * sizeof(unsigned), hipMemcpyHostToDevice, s)) != hipSuccess) return (int)e;
+    if (sides) {
+        hipError_t e = hipErrorInvalidValue;
+        tt.tic(2);
+        if (kind == 1) { UMPA_NW_SWITCH(dev.Nw, (e = launch_prep<1, NWC>(dev, M, st.sep, sides, s, PR))) }
+        else { UMPA_NW_SWITCH(dev.Nw, (e = launch_prep<0, NWC>(dev, M, st.sep, sides, s, PR))) }
+        tt.toc();
+        if (e != hipSuccess) return e;
+        st.ref_rect[0] = PR.tx0; st.ref_rect[1] = PR.tx1; st.ref_rect[2] = PR.ty0; st.ref_rect[3] = PR.ty1;
     }
+    st.ref_maps_ok = true; st.ref_kind = kind; st.ref_K = dev.Na; st.ref_plane = (size_t)M.H * M.W;
+    return hipSuccess;
+}
+
+// The row chunks of a match: chunk(drow0, drows, xi_lo, xi_hi) enqueues the kernels of the dense rows [drow0, drow0 + drows)
+// and of the output rows [xi_lo, xi_hi) whose dense row lies among them; then on_rows(xi_lo, xi_hi).  0 or the chunk's error.
+template <class Chunk>
+inline int tiled_chunks(TiledState& st, const RegionArgs& A, int N0d, long rows_chunk, const std::function<void(int, int)>& on_rows, Chunk chunk)
+{
+    st.stat_n = 0; st.stat_total_passes = 0.0;
     for (int drow0 = 0; drow0 < N0d; drow0 += (int)rows_chunk) {
         const int drows = (int)((N0d - drow0 < rows_chunk) ? N0d - drow0 : rows_chunk);
+        const int xi_lo = (drow0 + A.step0 - 1) / A.step0;
+        const int xi_hi = std::min(A.N0, (drow0 + drows - 1) / A.step0 + 1);
+        const int rc = chunk(drow0, drows, xi_lo, xi_hi);
+        if (rc != 0) return rc;
+        if (xi_hi > xi_lo && on_rows) on_rows(xi_lo, xi_hi);
+    }
+    return 0;
+}
+
+// the on-demand stages' geometry: the table kernel's tiles and passes
+inline OdArgs od_args(const CorrLaunch& CL)
+{
+    OdArgs od;
+    memset(&od, 0, sizeof(od));
+    od.tc = CL.tc; od.ub = CL.ub; od.nbatch = CL.nbatch; od.npass = CL.npass; od.ntx = CL.ntx; od.nty = CL.nty;
+    od.ub_inv = (65536 + CL.ub - 1) / CL.ub; od.nrow_inv = (65536 + CL.nrow - 1) / CL.nrow;
+    od.tr = UMPA_TILE;
+    return od;
+}
+
+// The counters of an on-demand chunk into the next page-locked slot: for umpa_hip_last_stats and, on the last launch of table
+// kernel `name` with `fma_per` FMAs per unit, for the FMA count of a timed match.
+inline hipError_t od_record(TiledState& st, const OdBuffers& B, hipStream_t s, TiledTimers& tt, int name, double fma_per,
+                            const int** slot_out = nullptr)
+{
+    int* slot = st.od_host + UMPA_OD_NCNT * (st.od_slot++ % UMPA_OD_SLOTS);
+    const hipError_t e = hipMemcpyAsync(slot, B.counters, UMPA_OD_NCNT * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return e;
+    if (st.stat_n < 64) st.stat_slots[st.stat_n++] = slot;
+    tt.attach(name, slot, fma_per);
+    if (slot_out) *slot_out = slot;
+    return hipSuccess;
+}
+
+// One row chunk on corr_volume's or corr_masked's table: every pass, or (`on_demand`) the passes the seed tiles predict and the
+// repair rounds ask for (od_run_chunk).  `table_name`: the table kernel's timer.  Returns 0, -3 or a positive hipError_t.
+template <class Corr, class Replay>
+inline int tiled_chunk(TiledState& st, const CorrLaunch& CL, bool on_demand, size_t npx, hipStream_t s, TiledTimers& tt,
+                       int table_name, Corr corr, Replay replay)
+{
+    const int ntiles = CL.ntx * CL.nty;
+    OdArgs od = od_args(CL);
+    hipError_t e;
+    if (on_demand) {
+        OdBuffers OB;
+        if (od_reserve(st, ntiles, CL.npass, npx, od, OB)) return -3;
+        if ((e = od_run_chunk(od, OB, s, corr, replay)) != hipSuccess) return (int)e;
+        if ((e = od_record(st, OB, s, tt, table_name, CL.fma_per_pass)) != hipSuccess) return (int)e;
+    } else {
+        od.mode = 0;
+        if ((e = corr(od)) != hipSuccess) return (int)e;
+        if ((e = replay(od)) != hipSuccess) return (int)e;
+    }
+    st.stat_total_passes += (double)ntiles * CL.npass;
+    return 0;
+}
+
+// One match of a region on the tiled path.  Returns 0, -3 (allocation) or a positive hipError_t.
+// `reuse_ref_maps`: the caller vouches that the reference frames are those of the previous call (it owns them).
+// `piece_rows` > 0: row chunks of at most that many dense rows (a multiple of 32) even where the table budget would
+// allow more (the host-array entry point downloads the rows of chunk c while chunk c+1 is being matched, the multi-GPU
+// leg sends them to rank 0); `on_rows(xi_lo, xi_hi)` is called after the kernels of a chunk have been enqueued.
+inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int W, const FrameBox& box, const RegionArgs& A,
+                       hipStream_t s, TiledTimers& tt, bool reuse_ref_maps,
+                       int piece_rows = 0, const std::function<void(int, int)>& on_rows = nullptr,
+                       const FrameDesc* host_frames = nullptr)      // a host copy of dev.frames (corr_march's staging offsets)
+{
+    const TiledEnv E = tiled_env();
+    const int K = dev.Na, Nw = dev.Nw, ms = dev.ms, UJ = 2 * ms - 1, sigma = dev.ref_mode ? -1 : 1;
+    Maps M;
+    if (tiled_maps(st, M, kind, K, H, W, box)) return -3;
+
+    // The table lives on the dense (unit-step) grid under the region: with step > 1 every step-th entry is used
+    // (tiled_applicable only sends small steps here).
+    const int N0d = A.step0 * (A.N0 - 1) + 1, N1d = A.step1 * (A.N1 - 1) + 1;
+    // table rows are padded to whole 256-byte tile rows: every (tile, row) of a plane is then a run of whole, aligned
+    // 128-byte lines (C2: 2028 -> 2048 doubles)
+    int N1p = (N1d + 31) / 32 * 32;
+    // wide windows: the table comes from corr_march (strip-blocked: [strip][rows][shift][tw], one "row" = nstrips * UJ^2 * tw doubles)
+    MarchPlan MP;
+    memset(&MP, 0, sizeof(MP));
+    MarchArgs MA0;                                                    // what every corr_march launch of the match shares
+    memset(&MA0, 0, sizeof(MA0));
+    if (host_frames && E.march) {
+        MP = march_plan(Nw, UJ, K, N1d);
+        if (MP.ok && !march_offsets(host_frames, K, sigma, box, MA0)) MP.ok = false;
+    }
+    if (MP.ok) N1p = MP.nstrips * MP.tw;                               // doubles per dense row and shift
+    // on-demand passes of corr_march (od_run_chunk_lattice): UMPA_HIP_ONDEMAND=1 on, =0 off
+    const bool march_od = E.ondemand > 0 && MP.ok && MP.npass >= 3 && MP.npass <= 64 && !E.ablate_march;
+    long rows_chunk = 0;
+    const int rc = tiled_table(st, E, (size_t)UJ * UJ * N1p, N0d, piece_rows, (size_t)N1p, rows_chunk);
+    if (rc != 0) return rc;
+    if (MP.ok) {
+        MA0.table = st.table; MA0.tw = MP.tw;
+        MA0.org0 = A.org0; MA0.org1 = A.org1; MA0.N1 = N1d; MA0.sigma = sigma;
+        MA0.br0 = box.r0; MA0.br1 = box.r1; MA0.bc0 = box.c0; MA0.bc1 = box.c1 + box.slack; MA0.Wf = box.Wf;
+        MA0.nstrips = MP.nstrips; MA0.npass = MP.npass; MA0.nuy = MP.nuy;
+        MA0.npa = MP.npa; MA0.npb = MP.npb; MA0.a_slot = MP.a_slot; MA0.b_slot = MP.b_slot; MA0.da = MP.da; MA0.db = MP.db;
+        MA0.ablate = E.ablate_march;
+    }
+
+    const hipError_t pe = tiled_prep(st, dev, M, A, kind, reuse_ref_maps, 1, s, tt);
+    if (pe != hipSuccess) return (int)pe;
+    const int ub = pick_ub(UJ);
+    // frame count as a template constant where the map planes are 32-bit addressable (eval_lookup)
+    const bool small = (size_t)M.H * M.W * 2 * sizeof(double) < ((size_t)1 << 32);   // a pair plane
+
+    return tiled_chunks(st, A, N0d, rows_chunk, on_rows, [&](int drow0, int drows, int xi_lo, int xi_hi) {
         CorrArgs CA;
         CA.table = st.table; CA.slot_stride = (size_t)drows * N1p; CA.pitch = N1p;
         CA.org0 = A.org0; CA.org1 = A.org1; CA.row0 = drow0; CA.rows = drows; CA.N1 = N1d;
-        CA.sigma = dev.ref_mode ? -1 : 1;
+        CA.sigma = sigma;
         CA.br0 = box.r0; CA.br1 = box.r1; CA.bc0 = box.c0; CA.bc1 = box.c1 + box.slack; CA.Wf = box.Wf;   // (pairs may start on column c1 then)
-        { const char* ab = getenv("UMPA_HIP_ABLATE"); CA.ablate = ab ? atoi(ab) : 0; }
+        CA.ablate = E.ablate;
         CA.ntx = CA.nty = 0;                                          // set by launch_corr for the tile shape it picks
-        // output rows whose dense row lies in [drow0, drow0 + drows)
-        const int xi_lo = (drow0 + A.step0 - 1) / A.step0;
-        const int xi_hi = std::min(A.N0, (drow0 + drows - 1) / A.step0 + 1);
         ReplayArgs R;
         R.table = st.table; R.slot_stride = CA.slot_stride; R.drow0 = drow0; R.N1d = N1p;
         R.strip_w = 0; R.tw = 0; R.drows = drows;
         if (MP.ok) { R.strip_w = MP.wo; R.tw = MP.tw; R.slot_stride = (size_t)MP.tw; }
-        {
-            const char* be = getenv("UMPA_HIP_REPLAY_BW");           // tuning: 64, 32, 16, 8, 4
-            const int bw = be ? atoi(be) : (MP.ok ? 32 : 16);
-            R.bw_log2 = bw >= 64 ? 6 : bw >= 32 ? 5 : bw >= 16 ? 4 : bw >= 8 ? 3 : 2;
-        }
+        R.bw_log2 = MP.ok ? 5 : 4;                                    // blocks of 32 x 2 pixels per wave on corr_march's table, else 16 x 4
         R.row0 = xi_lo; R.rows = std::max(0, xi_hi - xi_lo);
-        { const char* ab = getenv("UMPA_HIP_ABLATE_REPLAY"); R.ablate = ab ? atoi(ab) : 0; }
-        // frame count as a template constant where the map planes are 32-bit addressable (eval_lookup)
-        const bool small = (size_t)M.H * M.W * 2 * sizeof(double) < ((size_t)1 << 32);   // a pair plane
+        R.ablate = E.ablate_replay;
 
         CorrLaunch CL;
         memset(&CL, 0, sizeof(CL));
         CL.dry = true;                                                // which shape, how many passes?
-        e = hipErrorInvalidValue;
+        CL.shape = E.corr_shape;
+        hipError_t e = hipErrorInvalidValue;
         UMPA_NW_SWITCH(Nw, (e = launch_corr_nw<NWC>(ub, dev, CA, st.sep, s, CL)))
         if (e != hipSuccess) return (int)e;
         CL.dry = false;
         const int ntiles = CL.ntx * CL.nty;
-        const int* counts = nullptr;
-        double march_fma_full = 0.0;
 
         auto corr = [&](const OdArgs& od) {
             CL.od = od;
             hipError_t ce = hipErrorInvalidValue;
             if (MP.ok) {                                              // corr_march (od.mode is 0 here: the on-demand stages are corr_volume's)
-                MarchArgs MA;
-                memset(&MA, 0, sizeof(MA));
-                MA.table = st.table; MA.tw = MP.tw;
-                MA.org0 = A.org0; MA.org1 = A.org1; MA.row0 = drow0; MA.rows = drows; MA.N1 = N1d;
-                MA.sigma = CA.sigma;
-                MA.br0 = box.r0; MA.br1 = box.r1; MA.bc0 = box.c0; MA.bc1 = box.c1 + box.slack; MA.Wf = box.Wf;
-                MA.nstrips = MP.nstrips; MA.npass = MP.npass; MA.nuy = MP.nuy;
-                MA.npa = MP.npa; MA.npb = MP.npb; MA.a_slot = MP.a_slot; MA.b_slot = MP.b_slot; MA.da = MP.da; MA.db = MP.db;
-                MA.baseA = march_baseA; MA.baseB = march_baseB; MA.frame_off = st.march_off;
-                { const char* ab = getenv("UMPA_HIP_ABLATE_MARCH"); MA.ablate = ab ? atoi(ab) : 0; }
+                MarchArgs MA = MA0;
+                MA.row0 = drow0; MA.rows = drows;
                 if (od.done) {                                        // on-demand passes: the caller's bands, a part of the units
                     MA.nbands = od.nty; MA.band_rows = od.tr;
                     MA.done = od.done; MA.ndone = od.cnt0 ? od.cnt0 + OD_C_DONE : nullptr;
                     if (od.mode == 2) { MA.items = od.items; MA.nitems = od.cnt_out + OD_C_ITEMS; }
                 }
                 double fma = 0.0;
-                tic(9);
+                tt.tic(9);
                 ce = launch_march(dev, MA, st.sep, MP, s, &fma);
-                if (!od.done) march_fma_full = fma;
-                toc(od.done ? 0.0 : fma);                             // (on-demand: counted from the device's tally, below)
+                tt.toc(od.done ? 0.0 : fma);                          // (on-demand: counted from the device's tally, od_record)
                 return ce;
             }
-            tic(3);
+            tt.tic(3);
             UMPA_NW_SWITCH(Nw, (ce = launch_corr_nw<NWC>(ub, dev, CA, st.sep, s, CL)))
-            toc(od.mode ? 0.0 : CL.fma_per_pass * ntiles * CL.npass);
+            tt.toc(od.mode ? 0.0 : CL.fma_per_pass * ntiles * CL.npass);
             return ce;
         };
         auto replay = [&](const OdArgs& od) {
@@ -1341,22 +1394,17 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
                 // (profiles/r04_replay_blocks.txt): at C2 (28 KB of map window per block) eight L2s serve them faster than one -- 0.967
                 // against 0.916 ms --, at C3 (130 KB per block: 20 frames, +-7 shifts) the lines fetched eight times over are what
                 // counts -- 7.8 against 13.2 ms.  So: a multiple of 8 for large windows, never one for small ones (idle blocks on the right).
-                {
-                    const size_t window = (size_t)(bh + 2 * ms) * (bw + 2 * ms) * (((size_t)K + 1) / 2 * 16 + 16);
-                    const char* ge = getenv("UMPA_HIP_REPLAY_GRIDX");                 // tuning: 1 never a multiple of 8, 2 always
-                    const int gx = ge ? atoi(ge) : (kind == 1 && window > 65536 ? 2 : 1);
-                    if (gx == 1 && (grd.x & 7) == 0) grd.x += 1;
-                    if (gx == 2) grd.x = (grd.x + 7) / 8 * 8;
-                }
+                const size_t window = (size_t)(bh + 2 * ms) * (bw + 2 * ms) * (((size_t)K + 1) / 2 * 16 + 16);
+                if (kind == 1 && window > 65536) grd.x = (grd.x + 7) / 8 * 8;
+                else if ((grd.x & 7) == 0) grd.x += 1;
             }
             if (od.mode == 3) grd = dim3(2 * device_cu_count(), 1);   // queue over the parked pixels
             if (od.mode == 2 && od.sub > 1)                           // corr_march's sample lattice
                 grd = dim3(((A.N1 + od.sub - 1) / od.sub + 63) / 64, ((R.rows + od.sub - 1) / od.sub + UMPA_REPLAY_ROWS - 1) / UMPA_REPLAY_ROWS);
             if (od.mode == 1) { blk = dim3(64, 1); grd = dim3((32 * od.tc + 63) / 64, od_seed_count(od.ntx, od.c0) * od_seed_count(od.nty, od.r0)); if (!grd.y) return hipSuccess; }
-            static const int pad_lds = getenv("UMPA_HIP_REPLAY_PAD_LDS") ? atoi(getenv("UMPA_HIP_REPLAY_PAD_LDS")) : 0;   // diagnostics: occupancy
-            tic(4);
-#define UMPA_REPLAY_NA(n) case n: if (od.mode) hipLaunchKernelGGL((replay_walk_kernel<1, n, true>), grd, blk, pad_lds, s, dev, M, R, A, od); \
-                           else hipLaunchKernelGGL((replay_walk_kernel<1, n, false>), grd, blk, pad_lds, s, dev, M, R, A, od); break;
+            tt.tic(4);
+#define UMPA_REPLAY_NA(n) case n: if (od.mode) hipLaunchKernelGGL((replay_walk_kernel<1, n, true>), grd, blk, 0, s, dev, M, R, A, od); \
+                           else hipLaunchKernelGGL((replay_walk_kernel<1, n, false>), grd, blk, 0, s, dev, M, R, A, od); break;
             if (kind == 1 && small && dev.Na <= UMPA_KTEMPL) {
                 switch (dev.Na) {
                     UMPA_REPLAY_NA(1) UMPA_REPLAY_NA(2) UMPA_REPLAY_NA(3) UMPA_REPLAY_NA(4) UMPA_REPLAY_NA(5) UMPA_REPLAY_NA(6)
@@ -1365,81 +1413,47 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
                     UMPA_REPLAY_NA(19) UMPA_REPLAY_NA(20) UMPA_REPLAY_NA(21) UMPA_REPLAY_NA(22) UMPA_REPLAY_NA(23) UMPA_REPLAY_NA(24)
                 }
             } else if (kind == 1) {
-                if (od.mode) hipLaunchKernelGGL((replay_walk_kernel<1, 0, true>), grd, blk, pad_lds, s, dev, M, R, A, od);
-                else hipLaunchKernelGGL((replay_walk_kernel<1, 0, false>), grd, blk, pad_lds, s, dev, M, R, A, od);
-            } else if (od.mode) hipLaunchKernelGGL((replay_walk_kernel<0, 0, true>), grd, blk, pad_lds, s, dev, M, R, A, od);
-            else hipLaunchKernelGGL((replay_walk_kernel<0, 0, false>), grd, blk, pad_lds, s, dev, M, R, A, od);
+                if (od.mode) hipLaunchKernelGGL((replay_walk_kernel<1, 0, true>), grd, blk, 0, s, dev, M, R, A, od);
+                else hipLaunchKernelGGL((replay_walk_kernel<1, 0, false>), grd, blk, 0, s, dev, M, R, A, od);
+            } else if (od.mode) hipLaunchKernelGGL((replay_walk_kernel<0, 0, true>), grd, blk, 0, s, dev, M, R, A, od);
+            else hipLaunchKernelGGL((replay_walk_kernel<0, 0, false>), grd, blk, 0, s, dev, M, R, A, od);
 #undef UMPA_REPLAY_NA
-            toc();
+            tt.toc();
             return hipGetLastError();
         };
 
-        OdArgs od;
-        memset(&od, 0, sizeof(od));
-        od.tc = CL.tc; od.ub = CL.ub; od.nbatch = CL.nbatch; od.npass = CL.npass; od.ntx = CL.ntx; od.nty = CL.nty;
-        od.ub_inv = (65536 + CL.ub - 1) / CL.ub; od.nrow_inv = (65536 + CL.nrow - 1) / CL.nrow;
-        od.tr = UMPA_TILE;
-        OdBuffers OB;
-        int march_tiles = 0;
         if (march_od) {                                               // tiles = strips x bands of about UMPA_HIP_MARCH_OD_ROWS rows
-            const char* bt = getenv("UMPA_HIP_MARCH_OD_ROWS");      // (read per match: the tests set it)
-            const int band_target = bt ? std::max(32, atoi(bt)) : 512;
-            const int nb = std::max(1, (drows + band_target / 2) / band_target);
+            const int nb = std::max(1, (drows + E.march_od_rows / 2) / E.march_od_rows);
+            OdArgs od = od_args(CL);
             od.tc = MP.wo; od.tr = (drows + nb - 1) / nb; od.ntx = MP.nstrips; od.nty = nb;
             od.npass = MP.npass; od.nbatch = 1; od.ub = 64; od.ub_inv = 1024; od.nrow_inv = (65536 + MP.nuy - 1) / MP.nuy;
             od.alone = 1;
-            od.central = od_central_passes(ms, dev.ref_mode ? -1 : 1, MP.nuy, 1, 64, UJ);
-            march_tiles = od.ntx * od.nty;
-        }
-        if (march_od && march_tiles >= 2) {
-            if (od_reserve(st, march_tiles, MP.npass, (size_t)A.N0 * A.N1, od, OB)) return -3;
-            if ((e = od_run_chunk_lattice(od, OB, s, corr, replay, od_lattice_sub(8))) != hipSuccess) return (int)e;
-            int* slot = st.od_host + UMPA_OD_NCNT * (st.od_slot++ % UMPA_OD_SLOTS);
-            if ((e = hipMemcpyAsync(slot, OB.counters, UMPA_OD_NCNT * sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-            counts = slot;
-            if (st.stat_n < 64) st.stat_slots[st.stat_n++] = slot;
-            if (getenv("UMPA_HIP_OD_DEBUG")) {                        // diagnostics: the stages' counters (a host wait)
-                (void)hipStreamSynchronize(s);
-                fprintf(stderr, "march on-demand: %d tiles (%d strips x %d bands of %d rows) x %d passes\n", march_tiles, od.ntx, od.nty, od.tr, MP.npass);
-                for (int r = 0; r < OD_STAGES; r++)
-                    fprintf(stderr, "  stage %2d: tiles listed %6d  pixels parked %8d  units listed %6d  units done (stage 0: all) %6d\n",
-                            r, slot[8 * r + OD_C_TILES], slot[8 * r + OD_C_PX], slot[8 * r + OD_C_ITEMS], slot[8 * r + OD_C_DONE]);
-            }
-            {   // the FMAs of one unit: an exhaustive launch's over its units (the bands are equal but for the last)
-                MarchArgs MF;
-                memset(&MF, 0, sizeof(MF));
+            od.central = od_central_passes(ms, sigma, MP.nuy, 1, 64, UJ);
+            const int march_tiles = od.ntx * od.nty;
+            if (march_tiles >= 2) {
+                OdBuffers OB;
+                if (od_reserve(st, march_tiles, MP.npass, (size_t)A.N0 * A.N1, od, OB)) return -3;
+                if ((e = od_run_chunk_lattice(od, OB, s, corr, replay)) != hipSuccess) return (int)e;
+                MarchArgs MF;                                         // the FMAs of one unit: an exhaustive launch's over its units
+                memset(&MF, 0, sizeof(MF));                           // (the bands are equal but for the last)
                 MF.rows = drows; MF.nstrips = MP.nstrips; MF.npass = MP.npass; MF.nbands = od.nty; MF.band_rows = od.tr;
                 double f = 0.0;
                 march_fma(dev, MF, &f);
-                march_fma_full = f / ((double)march_tiles * MP.npass);
+                const int* slot = nullptr;
+                if ((e = od_record(st, OB, s, tt, 9, f / ((double)march_tiles * MP.npass), &slot)) != hipSuccess) return (int)e;
+                if (E.od_debug) {                                     // diagnostics: the stages' counters (a host wait)
+                    (void)hipStreamSynchronize(s);
+                    fprintf(stderr, "march on-demand: %d tiles (%d strips x %d bands of %d rows) x %d passes\n", march_tiles, od.ntx, od.nty, od.tr, MP.npass);
+                    for (int r = 0; r < OD_STAGES; r++)
+                        fprintf(stderr, "  stage %2d: tiles listed %6d  pixels parked %8d  units listed %6d  units done (stage 0: all) %6d\n",
+                                r, slot[8 * r + OD_C_TILES], slot[8 * r + OD_C_PX], slot[8 * r + OD_C_ITEMS], slot[8 * r + OD_C_DONE]);
+                }
+                st.stat_total_passes += (double)march_tiles * MP.npass;
+                return 0;
             }
-            if (tt) for (auto it = tt->entries.rbegin(); it != tt->entries.rend(); ++it)
-                if (it->name == 9) { it->counts = counts; it->fma_per = march_fma_full; break; }
-            st.stat_total_passes += (double)march_tiles * MP.npass - (double)ntiles * CL.npass;   // (the sum below adds ntiles * CL.npass)
-        } else if (!MP.ok && od_enabled(ntiles, CL.npass, false) && !CA.ablate) {
-            if (od_reserve(st, ntiles, CL.npass, (size_t)A.N0 * A.N1, od, OB)) return -3;
-            if (od_lattice_wanted()) {
-                od.alone = od_alone_wanted();
-                od.central = od_central_passes(ms, dev.ref_mode ? -1 : 1, CL.nrow, CL.nbatch, CL.ub, UJ);
-                e = od_run_chunk_lattice(od, OB, s, corr, replay, od_lattice_sub(4));
-            } else e = od_run_chunk(od, OB, s, corr, replay);
-            if (e != hipSuccess) return (int)e;
-            // the counters of this chunk, for the FMA count of a timed match and for umpa_hip_last_stats
-            int* slot = st.od_host + UMPA_OD_NCNT * (st.od_slot++ % UMPA_OD_SLOTS);
-            if ((e = hipMemcpyAsync(slot, OB.counters, UMPA_OD_NCNT * sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-            counts = slot;
-            if (st.stat_n < 64) st.stat_slots[st.stat_n++] = slot;
-            if (tt) for (auto it = tt->entries.rbegin(); it != tt->entries.rend(); ++it)
-                if (it->name == 3) { it->counts = counts; it->fma_per = CL.fma_per_pass; break; }   // all FMAs of the chunk on its last table launch
-        } else {
-            od.mode = 0;
-            if ((e = corr(od)) != hipSuccess) return (int)e;
-            if ((e = replay(od)) != hipSuccess) return (int)e;
         }
-        st.stat_total_passes += (double)ntiles * CL.npass;
-        if (xi_hi > xi_lo && on_rows) on_rows(xi_lo, xi_hi);
-    }
-    return 0;
+        return tiled_chunk(st, CL, !MP.ok && od_enabled(E, ntiles, CL.npass, false) && !CA.ablate, (size_t)A.N0 * A.N1, s, tt, 3, corr, replay);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1486,21 +1500,10 @@ inline hipError_t launch_masked_tc(const ModelDev& dev, MaskedArgs A, const Sep1
         const double per_shift_end = C::NPL * filt + 20.0 * C::TR * C::TC;
         L.fma_per_pass = (per_shift_frame * dev.Na + per_shift_end) * (double)UJ / nbatch;    // (UJ real column offsets over nbatch passes)
         if (L.dry) return hipSuccess;
-        static bool attr_set[64] = {};
-        int devid = 0;
-        (void)hipGetDevice(&devid);
-        {
-            std::lock_guard<std::mutex> lock(tiled_attr_mutex());
-            if (!attr_set[devid & 63]) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_masked_kernel<KIND, NW, UBM, TCT>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_masked_queue_kernel<KIND, NW, UBM, TCT>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS);
-                if (e != hipSuccess) return e;
-                attr_set[devid & 63] = true;
-            }
-        }
+        const int devid = current_device();
+        hipError_t e = set_lds_limit_once<&corr_masked_kernel<KIND, NW, UBM, TCT>>((int)C::LDS, devid);
+        if (e == hipSuccess) e = set_lds_limit_once<&corr_masked_queue_kernel<KIND, NW, UBM, TCT>>((int)C::LDS, devid);
+        if (e != hipSuccess) return e;
         const OdCorr oc = od_corr_args(L.od);
         if (L.od.mode == 2) {
             const int grid = ((device_cu_count() * C::WPC + 7) / 8) * 8;       // persistent: one workgroup per slot of the chip
@@ -1523,94 +1526,26 @@ inline hipError_t launch_masked(const ModelDev& dev, const MaskedArgs& A, const 
 
 // One match of a region of a masked model.  Returns 0, -3 (allocation) or a positive hipError_t.
 inline int tiled_match_masked(TiledState& st, const ModelDev& dev, int kind, int H, int W, const FrameBox& box, const RegionArgs& A,
-                              hipStream_t s, TiledTimers* tt, bool reuse_ref_maps, bool binary_masks,
+                              hipStream_t s, TiledTimers& tt, bool reuse_ref_maps, bool binary_masks,
                               int piece_rows = 0, const std::function<void(int, int)>& on_rows = nullptr)
 {
-    const int K = dev.Na, Nw = dev.Nw, ms = dev.ms, UJ = 2 * ms - 1, NV = kind == 1 ? 3 : 2;
-    const size_t plane = (size_t)H * W;
-    const size_t KP = ((size_t)K + 1) / 2;
+    const TiledEnv E = tiled_env();
+    const int Nw = dev.Nw, ms = dev.ms, UJ = 2 * ms - 1, NV = kind == 1 ? 3 : 2;
     Maps M;
-    M.H = H; M.W = W;
-    M.br0 = box.r0; M.br1 = box.r1; M.bc0 = box.c0; M.bc1 = box.c1; M.Wf = box.Wf;
-    M.SamSq = M.RefSq = M.WS = M.MR = nullptr;
+    memset(&M, 0, sizeof(M));
     if (kind == 1) {                                                   // the un-weighted reference means (Model.cpp:804-808): prep_maps' MR planes
-        const size_t nmaps = 2 + 4 * KP;
-        if (st.maps_cap < nmaps * plane) {
-            if (st.maps) (void)hipFree(st.maps);
-            st.maps = nullptr; st.maps_cap = 0;
-            st.ref_maps_ok = false;
-            if (hipMalloc((void**)&st.maps, nmaps * plane * sizeof(double)) != hipSuccess) return -3;
-            st.maps_cap = nmaps * plane;
-        }
-        if (st.ref_kind != kind || st.ref_K != K || st.ref_plane != plane) st.ref_maps_ok = false;
-        M.SamSq = st.maps; M.RefSq = st.maps + plane;
-        M.WS = st.maps + 2 * plane;
-        M.MR = st.maps + (2 + 2 * KP) * plane;
+        if (tiled_maps(st, M, kind, dev.Na, H, W, box)) return -3;
     }
     const int N0d = A.step0 * (A.N0 - 1) + 1, N1d = A.step1 * (A.N1 - 1) + 1;
-    const size_t row_bytes = (size_t)NV * UJ * UJ * N1d * sizeof(double);
-    long rows_chunk = (long)(tiled_table_budget() / row_bytes) / UMPA_TILE * UMPA_TILE;
-    if (rows_chunk < UMPA_TILE) rows_chunk = UMPA_TILE;
-    if (rows_chunk > N0d) rows_chunk = ((long)N0d + UMPA_TILE - 1) / UMPA_TILE * UMPA_TILE;
-    if (piece_rows > 0) {
-        const long want = ((long)piece_rows + UMPA_TILE - 1) / UMPA_TILE * UMPA_TILE;
-        if (want < rows_chunk) rows_chunk = want;
-    }
-    if (st.table_limited && st.table_cap > 0) {
-        const long fit = (long)(st.table_cap / ((size_t)NV * UJ * UJ * N1d)) / UMPA_TILE * UMPA_TILE;
-        if (fit >= UMPA_TILE && fit < rows_chunk) rows_chunk = fit;
-    }
-    size_t table_need = (size_t)NV * UJ * UJ * rows_chunk * N1d;
-    if (st.table_cap < table_need) {
-        if (st.table) (void)hipFree(st.table);
-        st.table = nullptr; st.table_cap = 0;
-        while (hipMalloc((void**)&st.table, table_need * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            st.table = nullptr;
-            if (rows_chunk <= UMPA_TILE) return -3;
-            st.table_limited = true;
-            rows_chunk = std::max<long>(UMPA_TILE, rows_chunk / 2 / UMPA_TILE * UMPA_TILE);
-            table_need = (size_t)NV * UJ * UJ * rows_chunk * N1d;
-        }
-        st.table_cap = table_need;
+    long rows_chunk = 0;
+    const int rc = tiled_table(st, E, (size_t)NV * UJ * UJ * N1d, N0d, piece_rows, 0, rows_chunk);   // (size_t slot strides)
+    if (rc != 0) return rc;
+    if (kind == 1) {                                                   // only the reference means are read: nothing to redo for a new sample stack
+        const hipError_t pe = tiled_prep(st, dev, M, A, kind, reuse_ref_maps, 0, s, tt);
+        if (pe != hipSuccess) return (int)pe;
     }
 
-    bool timing_open = false;
-    auto tic = [&](int name) {
-        timing_open = false;
-        if (!tt) return;
-        TiledTimers::Entry en = {name, tt->get(), tt->get(), 0.0, nullptr, 0.0};
-        if (!en.t0 || !en.t1) return;
-        (void)hipEventRecord(en.t0, s);
-        tt->entries.push_back(en);
-        timing_open = true;
-    };
-    auto toc = [&](double fma = 0.0) {
-        if (!timing_open) return;
-        tt->entries.back().fma = fma;
-        (void)hipEventRecord(tt->entries.back().t1, s);
-        timing_open = false;
-    };
-
-    hipError_t e = hipErrorInvalidValue;
-    if (kind == 1) {
-        PrepRect PRc = {0, 0, 0, 0};
-        UMPA_NW_SWITCH(Nw, (PRc = prep_rect<NWC>(M, A, ms)))
-        const bool covered = st.ref_rect[0] <= PRc.tx0 && st.ref_rect[1] >= PRc.tx1 && st.ref_rect[2] <= PRc.ty0 && st.ref_rect[3] >= PRc.ty1;
-        const int sides = (reuse_ref_maps && st.ref_maps_ok && covered) ? 0 : 3;   // only the reference means are read: nothing to redo for a new sample stack
-        st.ref_maps_ok = false;
-        if (sides) {
-            tic(2);
-            UMPA_NW_SWITCH(Nw, (e = launch_prep<1, NWC>(dev, M, st.sep, sides, s, PRc)))
-            toc();
-            if (e != hipSuccess) return (int)e;
-            st.ref_rect[0] = PRc.tx0; st.ref_rect[1] = PRc.tx1; st.ref_rect[2] = PRc.ty0; st.ref_rect[3] = PRc.ty1;
-        }
-        st.ref_maps_ok = true; st.ref_kind = kind; st.ref_K = K; st.ref_plane = plane;
-    }
-    st.stat_n = 0; st.stat_total_passes = 0.0;
-    for (int drow0 = 0; drow0 < N0d; drow0 += (int)rows_chunk) {
-        const int drows = (int)((N0d - drow0 < rows_chunk) ? N0d - drow0 : rows_chunk);
+    return tiled_chunks(st, A, N0d, rows_chunk, on_rows, [&](int drow0, int drows, int xi_lo, int xi_hi) {
         MaskedArgs MA;
         MA.table = st.table; MA.slot_stride = (size_t)drows * N1d;
         MA.MR = M.MR; MA.H = H; MA.W = W;
@@ -1619,15 +1554,13 @@ inline int tiled_match_masked(TiledState& st, const ModelDev& dev, int kind, int
         MA.br0 = box.r0; MA.br1 = box.r1; MA.bc0 = box.c0; MA.bc1 = box.c1; MA.Wf = box.Wf;
         MA.ntx = MA.nty = 0;
         MA.binary = binary_masks ? 1 : 0;
-        { const char* ab = getenv("UMPA_HIP_ABLATE_MASKED"); MA.ablate = ab ? atoi(ab) : 0; }
-        const int xi_lo = (drow0 + A.step0 - 1) / A.step0;
-        const int xi_hi = std::min(A.N0, (drow0 + drows - 1) / A.step0 + 1);
+        MA.ablate = E.ablate_masked;
         const int rrows = std::max(0, xi_hi - xi_lo);
 
         CorrLaunch CL;
         memset(&CL, 0, sizeof(CL));
         CL.dry = true;
-        e = hipErrorInvalidValue;
+        hipError_t e = hipErrorInvalidValue;
         if (kind == 1) { UMPA_NW_SWITCH(Nw, (e = launch_masked<1, NWC>(dev, MA, st.sep, s, CL))) }
         else { UMPA_NW_SWITCH(Nw, (e = launch_masked<0, NWC>(dev, MA, st.sep, s, CL))) }
         if (e != hipSuccess) return (int)e;
@@ -1637,53 +1570,25 @@ inline int tiled_match_masked(TiledState& st, const ModelDev& dev, int kind, int
         auto corr = [&](const OdArgs& od) {
             CL.od = od;
             hipError_t ce = hipErrorInvalidValue;
-            tic(6);
+            tt.tic(6);
             if (kind == 1) { UMPA_NW_SWITCH(Nw, (ce = launch_masked<1, NWC>(dev, MA, st.sep, s, CL))) }
             else { UMPA_NW_SWITCH(Nw, (ce = launch_masked<0, NWC>(dev, MA, st.sep, s, CL))) }
-            toc(od.mode ? 0.0 : CL.fma_per_pass * ntiles * CL.npass);
+            tt.toc(od.mode ? 0.0 : CL.fma_per_pass * ntiles * CL.npass);
             return ce;
         };
         auto replay = [&](const OdArgs& od) {
             if (rrows <= 0) return hipSuccess;
             dim3 blk(64), grd((A.N1 + 15) / 16, (rrows + 3) / 4);           // blocks of 16 x 4 pixels (modes 0 and 2)
             if (od.mode == 3) grd = dim3(2 * device_cu_count(), 1);
-            if (od.mode == 2 && od.sub > 1) grd = dim3(((A.N1 + od.sub - 1) / od.sub + 63) / 64, (rrows + od.sub - 1) / od.sub);   // the sample lattice
             if (od.mode == 1) { grd = dim3((32 * od.tc + 63) / 64, od_seed_count(od.ntx, od.c0) * od_seed_count(od.nty, od.r0)); if (!grd.y) return hipSuccess; }
-            tic(7);
+            tt.tic(7);
             if (kind == 1) hipLaunchKernelGGL((replay_cost_kernel<1>), grd, blk, 0, s, dev, (const double*)st.table, MA.slot_stride, drow0, N1d, xi_lo, rrows, A, od);
             else hipLaunchKernelGGL((replay_cost_kernel<0>), grd, blk, 0, s, dev, (const double*)st.table, MA.slot_stride, drow0, N1d, xi_lo, rrows, A, od);
-            toc();
+            tt.toc();
             return hipGetLastError();
         };
-
-        OdArgs od;
-        memset(&od, 0, sizeof(od));
-        od.tc = CL.tc; od.ub = CL.ub; od.nbatch = CL.nbatch; od.npass = CL.npass; od.ntx = CL.ntx; od.nty = CL.nty;
-        od.ub_inv = (65536 + CL.ub - 1) / CL.ub; od.nrow_inv = (65536 + CL.nrow - 1) / CL.nrow;
-        od.tr = UMPA_TILE;
-        OdBuffers OB;
-        if (od_enabled(ntiles, CL.npass, true) && !MA.ablate) {
-            if (od_reserve(st, ntiles, CL.npass, (size_t)A.N0 * A.N1, od, OB)) return -3;
-            if (od_lattice_wanted()) {
-                od.alone = od_alone_wanted();
-                od.central = od_central_passes(ms, dev.ref_mode ? -1 : 1, CL.nrow, CL.nbatch, CL.ub, UJ);
-                e = od_run_chunk_lattice(od, OB, s, corr, replay, od_lattice_sub(4));
-            } else e = od_run_chunk(od, OB, s, corr, replay);
-            if (e != hipSuccess) return (int)e;
-            int* slot = st.od_host + UMPA_OD_NCNT * (st.od_slot++ % UMPA_OD_SLOTS);
-            if ((e = hipMemcpyAsync(slot, OB.counters, UMPA_OD_NCNT * sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-            if (st.stat_n < 64) st.stat_slots[st.stat_n++] = slot;
-            if (tt) for (auto it = tt->entries.rbegin(); it != tt->entries.rend(); ++it)
-                if (it->name == 6) { it->counts = slot; it->fma_per = CL.fma_per_pass; break; }
-        } else {
-            od.mode = 0;
-            if ((e = corr(od)) != hipSuccess) return (int)e;
-            if ((e = replay(od)) != hipSuccess) return (int)e;
-        }
-        st.stat_total_passes += (double)ntiles * CL.npass;
-        if (xi_hi > xi_lo && on_rows) on_rows(xi_lo, xi_hi);
-    }
-    return 0;
+        return tiled_chunk(st, CL, od_enabled(E, ntiles, CL.npass, true) && !MA.ablate, (size_t)A.N0 * A.N1, s, tt, 6, corr, replay);
+    });
 }
 
 } // namespace umpa
