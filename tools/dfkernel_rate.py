@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Rate of the kernel-dark-field model (UMPAModelDFKernel, Model.cpp:997-1238) on one GPU: an E_dfkernel-type stack
 (2 frames, Nw=2, max_shift=4, per-pixel blur a=c=0.1, b=0) at 512 x 512, host-array API.
-UMPA_HIP_DFK_NO_REUSE=1 recomputes the 289-tap blur at every evaluation (round 1), the default fills the pixel's
-blurred footprint once."""
+Each pixel's blurred footprint is filled once (blur_tiles where the reference patch fits in LDS), not at every evaluation."""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -40,7 +39,6 @@ for q in range(lib.timing_collect(h)):
     lib.timing_read(h, q, ctypes.byref(nm), ctypes.byref(tot), ctypes.byref(cnt))
     kern[nm.value.decode()] = round(tot.value, 3)
 F = 2 * (Nw + ms - 1) + 1
-print(json.dumps(dict(reuse=not os.environ.get("UMPA_HIP_DFK_NO_REUSE"), tiles=not os.environ.get("UMPA_HIP_DFK_NO_TILES"),
-                      blur_fma_per_px=289 * F * F * K, blur_tfma_s=round(289.0 * F * F * K * N0 * N1 / dt / 1e12, 3), size=n, frames=K, Nw=Nw, max_shift=ms, output_px=N0 * N1,
+print(json.dumps(dict(blur_fma_per_px=289 * F * F * K, blur_tfma_s=round(289.0 * F * F * K * N0 * N1 / dt / 1e12, 3), size=n, frames=K, Nw=Nw, max_shift=ms, output_px=N0 * N1,
                       ms=round(dt * 1e3, 2), mpx_s=round(N0 * N1 / dt / 1e6, 2), err_ok=round(float(r["err"].mean()), 4),
                       Ncalls_mean=round(float(r["debug_Ncalls"].mean()), 2), kernels_ms=kern)))

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <mutex>
 #include <functional>
+#include <type_traits>
 
 #include "../../include/umpa_hip.h"
 #include "umpa_walk.h"
@@ -59,6 +60,66 @@ struct DevBuf {                       // grow-only device scratch
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// The per-pixel maps of a region (RegionArgs), in the order their copies are enqueued: the one list that slicing,
+// scratch and copies go through.  f(map, elements per pixel, planes, that map of each region): `values` holds nparam
+// doubles per pixel, interleaved (v_px = nparam) or planar (v_px = 1, plane k at k * v_k); `cover` is the one map the
+// kernels only read.  The regions share the first one's layout of `values`.
+enum { MAP_VALUES, MAP_ERR, MAP_UV, MAP_COVER, MAP_DBG_D, MAP_DBG_A, MAP_DBG_N, NMAPS };
+template <class F, class R0, class... R>
+void for_each_map(F f, R0& a, R&... r)
+{
+    const bool planar = a.v_px == 1 && a.nparam > 1;
+    f(MAP_VALUES, a.v_px, planar ? a.nparam : 1, a.values, r.values...);
+    f(MAP_ERR, 1, 1, a.err, r.err...);
+    f(MAP_UV, 2, 1, a.uv, r.uv...);
+    f(MAP_COVER, 1, 1, a.cover, r.cover...);
+    f(MAP_DBG_D, 25, 1, a.dbg_d, r.dbg_d...);
+    f(MAP_DBG_A, 16, 1, a.dbg_a, r.dbg_a...);
+    f(MAP_DBG_N, 1, 1, a.dbg_n, r.dbg_n...);
+}
+
+struct MapBufs {                      // device buffers for the maps of one region
+    DevBuf map[NMAPS];
+    void release() { for (DevBuf& b : map) b.release(); }
+};
+
+// Point the maps that A has at the buffers of `b`, each grown to n pixels; -1 if an allocation failed
+int use_bufs(RegionArgs& A, MapBufs& b, size_t n)
+{
+    int rc = 0;
+    for_each_map([&](int q, size_t per_px, int planes, auto*& p) {
+        if (!p) return;
+        if (b.map[q].reserve(n * per_px * planes * sizeof(*p))) rc = -1;
+        p = (std::remove_reference_t<decltype(p)>)b.map[q].p;
+    }, A);
+    return rc;
+}
+
+// The rectangle [r0,r1) x [c0,c1) of region A; its maps stay at A's row pitch
+RegionArgs sub_region(const RegionArgs& A, int r0, int r1, int c0, int c1)
+{
+    RegionArgs B = A;
+    B.org0 = A.org0 + A.step0 * r0; B.N0 = r1 - r0;
+    B.org1 = A.org1 + A.step1 * c0; B.N1 = c1 - c0;
+    const size_t off = (size_t)r0 * A.pitch + c0;
+    for_each_map([&](int, size_t per_px, int, auto*& p) { if (p) p += off * per_px; }, B);
+    return B;
+}
+
+// Copy the maps of S into those of D (device arrays of D.N0 x D.N1 pixels, each at its region's pitch): every map D
+// has but `cover`, and `cover` too if with_cover
+hipError_t copy_maps(const RegionArgs& D, const RegionArgs& S, bool with_cover, hipStream_t s)
+{
+    hipError_t e = hipSuccess;
+    for_each_map([&](int q, size_t per_px, int planes, auto* d, auto* src) {
+        const size_t epp = per_px * sizeof(*d);
+        for (int k = 0; d && (q != MAP_COVER || with_cover) && k < planes && e == hipSuccess; k++)
+            e = hipMemcpy2DAsync((void*)(d + k * D.v_k), D.pitch * epp, src + k * S.v_k, S.pitch * epp,
+                                 D.N1 * epp, (size_t)D.N0, hipMemcpyDeviceToDevice, s);
+    }, D, S);
+    return e;
+}
+
 } // namespace
 
 struct umpa_hip_model {
@@ -67,6 +128,7 @@ struct umpa_hip_model {
     bool has_mask = false, owns_frames = true;
     bool mask_binary = false;                      // every mask value is 0 or 1 (corr_masked's cheap pair weight)
     std::vector<int> dims, pos;
+    size_t frame_total = 0;                        // elements of all frames together
     std::vector<double*> d_sam, d_ref, d_mask;     // device frame pointers
     void* d_frames_blob = nullptr;                 // one allocation holding all owned frames
     FrameDesc* d_desc = nullptr;
@@ -100,9 +162,9 @@ struct umpa_hip_model {
     FrameDesc* h_desc = nullptr;                   // pinned host copy of the descriptor table (source of the stream-ordered update)
     // device copies of a host-array match's arrays, two sets: the maps of match p travel to the host while match p + 1
     // (the step-scan pipeline, umpa_amd/farm.py) already writes the other set
-    DevBuf b_values[2], b_uv[2], b_err[2], b_cover[2], b_dd[2], b_da[2], b_dn[2];
+    MapBufs b[2];
     DevBuf b_covout, b_small, b_kern;
-    DevBuf t_values, t_uv, t_err, t_cover, t_dd, t_da, t_dn;   // dense outputs of a sub-rectangle (sample-stepping split)
+    MapBufs t;                                     // dense maps of a sub-rectangle (sample-stepping split)
     TiledState tiled;                              // scratch of the tiled fast path
     int last_path = 0;
     bool timing = false;
@@ -152,6 +214,40 @@ struct ScopedTimer {                   // brackets a launch with events when tim
     }
 };
 
+// parameters per pixel of a model kind (Model.cpp: T, dx, dy, f; dark field: + df; kernel dark field: + a, b, c)
+int kind_nparam(int kind) { return kind == UMPA_HIP_KIND_DF ? 5 : kind == UMPA_HIP_KIND_DFKERNEL ? 7 : 4; }
+
+FrameDesc frame_desc(const umpa_hip_model* m, int k)
+{
+    FrameDesc f{};
+    f.sam = m->d_sam[k]; f.ref = m->d_ref[k]; f.mask = m->d_mask[k];
+    f.H = m->dims[2 * k]; f.W = m->dims[2 * k + 1]; f.pi = m->pos[2 * k]; f.pj = m->pos[2 * k + 1];
+    return f;
+}
+
+std::vector<FrameDesc> frame_list(const umpa_hip_model* m)
+{
+    std::vector<FrameDesc> f(m->Na);
+    for (int k = 0; k < m->Na; k++) f[k] = frame_desc(m, k);
+    return f;
+}
+
+// the box of image rows / columns that lies inside every frame of the list
+FrameBox frame_box(const std::vector<FrameDesc>& frames, int Wf, int slack)
+{
+    FrameBox b = {0, 1 << 30, 0, 1 << 30, Wf, slack};
+    for (const FrameDesc& f : frames) {
+        b.r0 = std::max(b.r0, f.pi); b.r1 = std::min(b.r1, f.pi + f.H - 1);
+        b.c0 = std::max(b.c0, f.pj); b.c1 = std::min(b.c1, f.pj + f.W - 1);
+    }
+    return b;
+}
+
+// Region pixel indices along one axis (pixel q at org + step * q, 0 <= q < N): the first pixel at or after v (index_lo)
+// and one past the last pixel at or before v (index_hi)
+int index_lo(int v, int org, int step, int N) { int q = v - org; q = q <= 0 ? 0 : (q + step - 1) / step; return std::min(q, N); }
+int index_hi(int v, int org, int step, int N) { int q = v - org; q = q < 0 ? 0 : q / step + 1; return std::min(q, N); }
+
 int upload_win(umpa_hip_model* m, const double* win, int Nw)
 {
     const int S = 2 * Nw + 1;
@@ -196,24 +292,13 @@ void launch_direct_nw(umpa_hip_model* m, const RegionArgs& A, hipStream_t s)
                        m->dev(), A, nbx, nby);
 }
 
-// the window half-widths of practical use get their own instantiation (unrolled window rows); the kernel-dark-field
-// model and anything else run the generic one
+// the window half-widths of practical use get their own instantiation (unrolled window rows), for the kernel-dark-field
+// model too (its evaluations read the pixel's blurred footprint a window row at a time, all loads of a row in flight);
+// any other runs the generic one
 template <int KIND, bool MASK>
 void launch_direct(umpa_hip_model* m, const RegionArgs& A, hipStream_t s)
 {
-    {                                                                 // (the kernel-dark-field model too: its evaluations read the pixel's
-        switch (m->Nw) {                                                // blurred footprint a window row at a time, all loads of a row in flight)
-        case 1: return launch_direct_nw<KIND, MASK, 1>(m, A, s);
-        case 2: return launch_direct_nw<KIND, MASK, 2>(m, A, s);
-        case 3: return launch_direct_nw<KIND, MASK, 3>(m, A, s);
-        case 4: return launch_direct_nw<KIND, MASK, 4>(m, A, s);
-        case 5: return launch_direct_nw<KIND, MASK, 5>(m, A, s);
-        case 6: return launch_direct_nw<KIND, MASK, 6>(m, A, s);
-        case 7: return launch_direct_nw<KIND, MASK, 7>(m, A, s);
-        case 8: return launch_direct_nw<KIND, MASK, 8>(m, A, s);
-        default: break;
-        }
-    }
+    UMPA_NW_SWITCH(m->Nw, return (launch_direct_nw<KIND, MASK, NWC>(m, A, s)))
     launch_direct_nw<KIND, MASK, 0>(m, A, s);
 }
 
@@ -253,95 +338,75 @@ hipError_t launch_staged_nw(umpa_hip_model* m, const RegionArgs& A, const Staged
     return hipGetLastError();
 }
 
-template <int KIND, bool MASK>
+// (no masked instantiation: masked models never take the staged kernel -- run_direct -- and run on the tiled path,
+// umpa_masked.h)
 hipError_t launch_staged(umpa_hip_model* m, const RegionArgs& A, const StagedGeom& G, size_t lds_bytes, hipStream_t s)
 {
-    switch (m->Nw) {
-    case 1: return launch_staged_nw<KIND, MASK, 1>(m, A, G, lds_bytes, s);
-    case 2: return launch_staged_nw<KIND, MASK, 2>(m, A, G, lds_bytes, s);
-    case 3: return launch_staged_nw<KIND, MASK, 3>(m, A, G, lds_bytes, s);
-    case 4: return launch_staged_nw<KIND, MASK, 4>(m, A, G, lds_bytes, s);
-    case 5: return launch_staged_nw<KIND, MASK, 5>(m, A, G, lds_bytes, s);
-    case 6: return launch_staged_nw<KIND, MASK, 6>(m, A, G, lds_bytes, s);
-    case 7: return launch_staged_nw<KIND, MASK, 7>(m, A, G, lds_bytes, s);
-    case 8: return launch_staged_nw<KIND, MASK, 8>(m, A, G, lds_bytes, s);
-    default: return launch_staged_nw<KIND, MASK, 0>(m, A, G, lds_bytes, s);
+    if (m->kind == UMPA_HIP_KIND_NODF) {
+        UMPA_NW_SWITCH(m->Nw, return (launch_staged_nw<0, false, NWC>(m, A, G, lds_bytes, s)))
+        return launch_staged_nw<0, false, 0>(m, A, G, lds_bytes, s);
     }
+    UMPA_NW_SWITCH(m->Nw, return (launch_staged_nw<1, false, NWC>(m, A, G, lds_bytes, s)))
+    return launch_staged_nw<1, false, 0>(m, A, G, lds_bytes, s);
 }
 
-int run_direct(umpa_hip_model* m, const RegionArgs& A0, hipStream_t s, int flags = 0)
+// The kernel-dark-field model: every pixel carries its own 17x17 blur kernel (Model.cpp:88-117: 289 doubles) and the
+// reference blurred with it over the footprint its evaluations read (blur_footprint: Na * F * F doubles).  The region
+// is matched in row chunks whose scratch stays below 2 GiB.
+int run_dfkernel(umpa_hip_model* m, const RegionArgs& A, hipStream_t s)
 {
-    RegionArgs A = A0;
-    A.kern = nullptr; A.kern_stride = 0; A.row_base = 0; A.blur = nullptr; A.blur_F = 0; A.blur_ready = 0;
+    const int halo = m->Nw + (m->ref_mode ? 0 : std::max(m->ms - 1, 0));    // the reference window moves in 'sam' mode only
+    const int F = 2 * halo + 1;
+    const size_t per_row = ((size_t)UMPA_BLUR_TAPS + (size_t)m->Na * F * F) * A.N1 * sizeof(double);
+    int rows_chunk = (int)std::max<size_t>(1, ((size_t)2 << 30) / per_row);
+    rows_chunk = std::min(rows_chunk, A.N0);
+    if (m->b_kern.reserve(per_row * rows_chunk)) return fail(UMPA_HIP_E_NOMEM, "blur-kernel scratch");
+    for (int row0 = 0; row0 < A.N0; row0 += rows_chunk) {
+        RegionArgs C = sub_region(A, row0, std::min(row0 + rows_chunk, A.N0), 0, A.N1);
+        C.kern = (double*)m->b_kern.p; C.kern_stride = (size_t)C.N0 * C.N1; C.row_base = 0;
+        C.blur = C.kern + (size_t)UMPA_BLUR_TAPS * C.kern_stride;
+        C.blur_F = F;
+        C.blur_ready = 0;
+        // the footprints of a 64 x 4 pixel box at a time, reference patch staged in LDS (blur_tiles_kernel); where the
+        // patch does not fit (large steps) each lane fills its own
+        const BlurTileGeom BG = blur_tile_geometry(halo, C.step0, C.step1);
+        const size_t blur_lds = (size_t)BG.PR * BG.PC * sizeof(double) * (m->has_mask ? 2 : 1);
+        if (blur_lds <= (size_t)UMPA_LDS_BUDGET / 2) {
+            const hipError_t be = m->has_mask ? set_lds_limit_once<&blur_tiles_kernel<true>>(UMPA_LDS_BUDGET / 2, m->device)
+                                              : set_lds_limit_once<&blur_tiles_kernel<false>>(UMPA_LDS_BUDGET / 2, m->device);
+            if (be != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "blur_tiles attribute: %s", hipGetErrorString(be));
+            dim3 bgrid((C.N1 + UMPA_BLURT_BX - 1) / UMPA_BLURT_BX, (C.N0 + UMPA_BLURT_BY - 1) / UMPA_BLURT_BY), bblk(UMPA_BLURT_BX, UMPA_BLURT_BY);
+            {
+                ScopedTimer t(m, s, KN_BLUR);
+                if (m->has_mask) hipLaunchKernelGGL((blur_tiles_kernel<true>), bgrid, bblk, blur_lds, s, m->dev(), C, BG);
+                else hipLaunchKernelGGL((blur_tiles_kernel<false>), bgrid, bblk, blur_lds, s, m->dev(), C, BG);
+            }
+            HIP_TRY(hipGetLastError(), UMPA_HIP_E_LAUNCH);
+            C.blur_ready = 1;
+        }
+        if (m->has_mask) launch_direct<2, true>(m, C, s); else launch_direct<2, false>(m, C, s);
+        HIP_TRY(hipGetLastError(), UMPA_HIP_E_LAUNCH);
+    }
+    m->last_path = 1;
+    return 0;
+}
+
+int run_direct(umpa_hip_model* m, const RegionArgs& A, hipStream_t s, int flags = 0)
+{
     // the staged kernel (windows out of LDS) for regions of more than a few pixels whose footprints fit; the plain one
     // (windows through L1) for the kernel-dark-field model, single pixels, large steps, or on request
-    static const bool no_staged = getenv("UMPA_HIP_NO_STAGED") != nullptr;
     StagedGeom G;
     size_t lds_bytes = 0;
     // (with masks the staged kernel is the slower one -- three footprints leave room for one workgroup per CU and the
     // weights make the summation VALU-bound: 225 against 152 ms on C2 -- so masked models stay on match_direct)
-    if (m->kind != UMPA_HIP_KIND_DFKERNEL && !m->has_mask && !no_staged && !(flags & UMPA_HIP_F_FORCE_PLAIN_DIRECT) &&
+    if (m->kind != UMPA_HIP_KIND_DFKERNEL && !m->has_mask && !(flags & UMPA_HIP_F_FORCE_PLAIN_DIRECT) &&
         (size_t)A.N0 * A.N1 >= 64 && A.N1 >= 8 && staged_geometry(m, A, G, lds_bytes)) {      // (a column or two: one lane per workgroup row would work)
-        hipError_t e;
-        // (no masked instantiation: masked models never come here -- above -- and run on the tiled path, umpa_masked.h)
-        if (m->kind == UMPA_HIP_KIND_NODF) e = launch_staged<0, false>(m, A, G, lds_bytes, s);
-        else e = launch_staged<1, false>(m, A, G, lds_bytes, s);
+        const hipError_t e = launch_staged(m, A, G, lds_bytes, s);
         if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "staged kernel: %s", hipGetErrorString(e));
         m->last_path = 3;
         return 0;
     }
-    if (m->kind == UMPA_HIP_KIND_DFKERNEL) {
-        // every pixel carries its own 17x17 blur kernel (Model.cpp:88-117: 289 doubles) and, unless UMPA_HIP_DFK_NO_REUSE
-        // is set, the reference blurred with it over the footprint its evaluations read (blur_footprint: Na * F * F
-        // doubles): the region is matched in row chunks whose scratch stays below 2 GiB
-        static const bool no_reuse = getenv("UMPA_HIP_DFK_NO_REUSE") != nullptr;
-        const int halo = m->Nw + (m->ref_mode ? 0 : std::max(m->ms - 1, 0));    // the reference window moves in 'sam' mode only
-        const int F = 2 * halo + 1;
-        const size_t per_px = (size_t)UMPA_BLUR_TAPS + (no_reuse ? 0 : (size_t)m->Na * F * F);
-        const size_t per_row = per_px * A.N1 * sizeof(double);
-        int rows_chunk = (int)std::max<size_t>(1, ((size_t)2 << 30) / per_row);
-        rows_chunk = std::min(rows_chunk, A.N0);
-        if (m->b_kern.reserve(per_row * rows_chunk)) return fail(UMPA_HIP_E_NOMEM, "blur-kernel scratch");
-        for (int row0 = 0; row0 < A0.N0; row0 += rows_chunk) {
-            RegionArgs C = A0;
-            const size_t px0 = (size_t)row0 * A0.N1;
-            C.org0 = A0.org0 + A0.step0 * row0;
-            C.N0 = std::min(rows_chunk, A0.N0 - row0);
-            C.values = A0.values + px0 * A0.v_px;
-            C.uv = A0.uv ? A0.uv + 2 * px0 : nullptr;
-            C.err = A0.err + px0;
-            C.cover = A0.cover ? A0.cover + px0 : nullptr;
-            C.dbg_d = A0.dbg_d ? A0.dbg_d + 25 * px0 : nullptr;
-            C.dbg_a = A0.dbg_a ? A0.dbg_a + 16 * px0 : nullptr;
-            C.dbg_n = A0.dbg_n ? A0.dbg_n + px0 : nullptr;
-            C.kern = (double*)m->b_kern.p; C.kern_stride = (size_t)C.N0 * C.N1; C.row_base = 0;
-            C.blur = no_reuse ? nullptr : C.kern + (size_t)UMPA_BLUR_TAPS * C.kern_stride;
-            C.blur_F = F;
-            C.blur_ready = 0;
-            // the footprints of a 64 x 4 pixel box at a time, reference patch staged in LDS (blur_tiles_kernel); where the
-            // patch does not fit (large steps) or on request (UMPA_HIP_DFK_NO_TILES) each lane fills its own as before
-            static const bool no_tiles = getenv("UMPA_HIP_DFK_NO_TILES") != nullptr;
-            const BlurTileGeom BG = blur_tile_geometry(halo, C.step0, C.step1);
-            const size_t blur_lds = (size_t)BG.PR * BG.PC * sizeof(double) * (m->has_mask ? 2 : 1);
-            if (!no_reuse && !no_tiles && blur_lds <= (size_t)UMPA_LDS_BUDGET / 2) {
-                const hipError_t be = m->has_mask ? set_lds_limit_once<&blur_tiles_kernel<true>>(UMPA_LDS_BUDGET / 2, m->device)
-                                                  : set_lds_limit_once<&blur_tiles_kernel<false>>(UMPA_LDS_BUDGET / 2, m->device);
-                if (be != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "blur_tiles attribute: %s", hipGetErrorString(be));
-                dim3 bgrid((C.N1 + UMPA_BLURT_BX - 1) / UMPA_BLURT_BX, (C.N0 + UMPA_BLURT_BY - 1) / UMPA_BLURT_BY), bblk(UMPA_BLURT_BX, UMPA_BLURT_BY);
-                {
-                    ScopedTimer t(m, s, KN_BLUR);
-                    if (m->has_mask) hipLaunchKernelGGL((blur_tiles_kernel<true>), bgrid, bblk, blur_lds, s, m->dev(), C, BG);
-                    else hipLaunchKernelGGL((blur_tiles_kernel<false>), bgrid, bblk, blur_lds, s, m->dev(), C, BG);
-                }
-                HIP_TRY(hipGetLastError(), UMPA_HIP_E_LAUNCH);
-                C.blur_ready = 1;
-            }
-            if (m->has_mask) launch_direct<2, true>(m, C, s); else launch_direct<2, false>(m, C, s);
-            HIP_TRY(hipGetLastError(), UMPA_HIP_E_LAUNCH);
-        }
-        m->last_path = 1;
-        return 0;
-    }
+    if (m->kind == UMPA_HIP_KIND_DFKERNEL) return run_dfkernel(m, A, s);
     if (m->kind == UMPA_HIP_KIND_NODF) { if (m->has_mask) launch_direct<0, true>(m, A, s); else launch_direct<0, false>(m, A, s); }
     else { if (m->has_mask) launch_direct<1, true>(m, A, s); else launch_direct<1, false>(m, A, s); }
     HIP_TRY(hipGetLastError(), UMPA_HIP_E_LAUNCH);
@@ -379,12 +444,10 @@ bool tiled_applicable(const umpa_hip_model* m, const RegionArgs& A, bool forced 
     // one there.  The table grows with the number of shifts, the direct walk does not: the limit scales with 81 / planes.
     // Masked models cost 7x (NoDF 2x) more per dense pixel on the tiled path and about the same on the direct one.
     {
-        static const char* se = getenv("UMPA_HIP_TILED_MAX_STEP2");   // tuning override
         const int planes = (2 * m->ms - 1) * (2 * m->ms - 1);
         const int base = !m->has_mask ? 64 : m->kind == UMPA_HIP_KIND_NODF ? 16 : 5;
         int lim = planes <= 81 ? base : base * 81 / planes;
         if (lim < 1) lim = 1;
-        if (se) lim = atoi(se);
         if (forced && lim < 81) lim = 81;                              // UMPA_HIP_F_FORCE_TILED: the caller's choice, not the economics
         if (A.step0 * A.step1 > lim) return false;
     }
@@ -412,27 +475,21 @@ StepGeom step_geometry(const umpa_hip_model* m, const RegionArgs& A)
 {
     StepGeom g;
     g.any_pos = false;
-    int r0 = 0, r1 = 1 << 30, c0 = 0, c1 = 1 << 30;
     g.Himg = g.Wimg = 0;
-    for (int k = 0; k < m->Na; k++) {
-        const int pi = m->pos[2 * k], pj = m->pos[2 * k + 1], H = m->dims[2 * k], W = m->dims[2 * k + 1];
-        if (pi || pj) g.any_pos = true;
-        r0 = std::max(r0, pi); r1 = std::min(r1, pi + H - 1);
-        c0 = std::max(c0, pj); c1 = std::min(c1, pj + W - 1);
-        g.Himg = std::max(g.Himg, pi + H); g.Wimg = std::max(g.Wimg, pj + W);
+    const std::vector<FrameDesc> frames = frame_list(m);
+    for (const FrameDesc& f : frames) {
+        if (f.pi || f.pj) g.any_pos = true;
+        g.Himg = std::max(g.Himg, f.pi + f.H); g.Wimg = std::max(g.Wimg, f.pj + f.W);
     }
-    g.box.r0 = r0; g.box.r1 = r1; g.box.c0 = c0; g.box.c1 = c1; g.box.Wf = m->dims[1];
-    // a frame contributes at image pixel (i, j) iff i - pi - pad >= 0 and i - pi + pad <= H (same for j)
-    const int pad = m->padding;
     // (the last contributing column, j = c1 + 1 - pad, would make corr_volume read the very last column of a frame as the
     // first half of a 16-byte column pair: it is left to the border strip)
     // -- unless 8 readable bytes follow every frame (pair_slack: frames the library owns, models without masks)
-    g.box.slack = pair_slack(m) ? 1 : 0;
-    const int imin = r0 + pad, imax = r1 + 1 - pad, jmin = c0 + pad, jmax = c1 - pad + g.box.slack;
-    auto lo = [](int vmin, int org, int step, int N) { int q = vmin - org; q = q <= 0 ? 0 : (q + step - 1) / step; return std::min(q, N); };
-    auto hi = [](int vmax, int org, int step, int N) { int q = vmax - org; q = q < 0 ? 0 : q / step + 1; return std::min(q, N); };
-    g.a0 = lo(imin, A.org0, A.step0, A.N0); g.b0 = std::max(g.a0, hi(imax, A.org0, A.step0, A.N0));
-    g.a1 = lo(jmin, A.org1, A.step1, A.N1); g.b1 = std::max(g.a1, hi(jmax, A.org1, A.step1, A.N1));
+    g.box = frame_box(frames, m->dims[1], pair_slack(m) ? 1 : 0);
+    // a frame contributes at image pixel (i, j) iff i - pi - pad >= 0 and i - pi + pad <= H (same for j)
+    const int pad = m->padding;
+    const int imin = g.box.r0 + pad, imax = g.box.r1 + 1 - pad, jmin = g.box.c0 + pad, jmax = g.box.c1 - pad + g.box.slack;
+    g.a0 = index_lo(imin, A.org0, A.step0, A.N0); g.b0 = std::max(g.a0, index_hi(imax, A.org0, A.step0, A.N0));
+    g.a1 = index_lo(jmin, A.org1, A.step1, A.N1); g.b1 = std::max(g.a1, index_hi(jmax, A.org1, A.step1, A.N1));
     return g;
 }
 
@@ -448,14 +505,7 @@ int run_tiled(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int fla
     if (sub) { dev.frames = sub->frames; dev.Na = sub->n; m->tiled.ref_maps_ok = false; }      // (Nwt stays the model's frame count)
     const bool reuse = !sub && (flags & UMPA_HIP_F_REUSE_REF_MAPS) != 0;
     std::vector<FrameDesc> hf;                                        // a host copy of the frame list (corr_march's staging offsets)
-    if (!sub) {
-        hf.resize(m->Na);
-        for (int k = 0; k < m->Na; k++) {
-            memset(&hf[k], 0, sizeof(FrameDesc));
-            hf[k].sam = m->d_sam[k]; hf[k].ref = m->d_ref[k]; hf[k].mask = m->d_mask[k];
-            hf[k].H = m->dims[2 * k]; hf[k].W = m->dims[2 * k + 1]; hf[k].pi = m->pos[2 * k]; hf[k].pj = m->pos[2 * k + 1];
-        }
-    }
+    if (!sub) hf = frame_list(m);
     int rc = m->has_mask
         ? tiled_match_masked(m->tiled, dev, m->kind, g.Himg, g.Wimg, sub ? sub->box : g.box, A, s,
                              tt, reuse, m->mask_binary, piece_rows, on_rows)
@@ -467,73 +517,27 @@ int run_tiled(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int fla
     return 0;
 }
 
-// copy a block of pixels (rows x cols, `epp` bytes per pixel) between two row-major pixel arrays on the device
-hipError_t copy_block(void* dst, int dN1, int dr, int dc, const void* src, int sN1, int sr, int sc,
-                      int rows, int cols, size_t epp, hipStream_t s)
-{
-    if (rows <= 0 || cols <= 0) return hipSuccess;
-    return hipMemcpy2DAsync((char*)dst + ((size_t)dr * dN1 + dc) * epp, (size_t)dN1 * epp,
-                            (const char*)src + ((size_t)sr * sN1 + sc) * epp, (size_t)sN1 * epp,
-                            (size_t)cols * epp, (size_t)rows, hipMemcpyDeviceToDevice, s);
-}
-
-// One sub-rectangle [r0,r1) x [c0,c1) of the region, matched into dense scratch arrays and copied back: `tiled` sends
-// it down the tiled path (every frame contributes everywhere in it), otherwise the general kernels take it.
+// One sub-rectangle [r0,r1) x [c0,c1) of the region: `tiled` sends it down the tiled path (every frame contributes
+// everywhere in it), otherwise the general kernels take it.
 int run_block(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int r0, int r1, int c0, int c1, bool tiled,
               int flags, hipStream_t s, const FrameSubset* sub = nullptr)
 {
-    if (tiled) {
-        // the tiled kernels write this rectangle of the full arrays in place (row pitch = the full region's): nothing is
-        // copied, pixels below the coverage threshold keep what they had
-        RegionArgs B = A;
-        const size_t off = (size_t)r0 * A.pitch + c0;
-        B.org0 = A.org0 + A.step0 * r0; B.N0 = r1 - r0;
-        B.org1 = A.org1 + A.step1 * c0; B.N1 = c1 - c0;
-        if (B.N0 <= 0 || B.N1 <= 0) return 0;
-        B.values = A.values + off * A.v_px; B.err = A.err + off;
-        if (A.uv) B.uv = A.uv + 2 * off;
-        if (A.cover) B.cover = A.cover + off;
-        if (A.dbg_d) B.dbg_d = A.dbg_d + 25 * off;
-        if (A.dbg_a) B.dbg_a = A.dbg_a + 16 * off;
-        if (A.dbg_n) B.dbg_n = A.dbg_n + off;
-        return run_tiled(m, B, g, flags, s, 0, nullptr, sub);
-    }
-    const bool keep_in = true;                                        // pixels the kernels may leave untouched: coverage threshold
-    const int rows = r1 - r0, cols = c1 - c0;
-    if (rows <= 0 || cols <= 0) return 0;
-    const size_t n = (size_t)rows * cols, nfull = (size_t)A.N0 * A.N1;
-    const bool planar = A.v_px == 1 && A.nparam > 1;
-    const int np = A.nparam;
-    if (m->t_values.reserve(n * np * sizeof(double)) || m->t_err.reserve(n * sizeof(int))) return fail(UMPA_HIP_E_NOMEM, "block scratch");
-    RegionArgs B = A;
-    B.org0 = A.org0 + A.step0 * r0; B.N0 = rows;
-    B.org1 = A.org1 + A.step1 * c0; B.N1 = cols; B.pitch = cols;
-    B.values = (double*)m->t_values.p; B.err = (int*)m->t_err.p;
-    B.v_px = planar ? 1 : (size_t)np; B.v_k = planar ? n : 1;
-    B.uv = nullptr; B.cover = nullptr; B.dbg_d = nullptr; B.dbg_a = nullptr; B.dbg_n = nullptr;
-    hipError_t e = hipSuccess;
-    auto in = [&](void* t, const void* full, size_t epp) { if (e == hipSuccess) e = copy_block(t, cols, 0, 0, full, A.N1, r0, c0, rows, cols, epp, s); };
-    auto out = [&](void* full, const void* t, size_t epp) { if (e == hipSuccess) e = copy_block(full, A.N1, r0, c0, t, cols, 0, 0, rows, cols, epp, s); };
-    // what the kernels may leave untouched (pixels below the coverage threshold) must come back as it was
-    if (keep_in) {
-        if (planar) for (int k = 0; k < np; k++) in(B.values + (size_t)k * n, A.values + (size_t)k * nfull, sizeof(double));
-        else in(B.values, A.values, np * sizeof(double));
-        in(B.err, A.err, sizeof(int));
-    }
-    if (A.uv) { if (m->t_uv.reserve(n * 2 * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "block scratch"); B.uv = (double*)m->t_uv.p; in(B.uv, A.uv, 2 * sizeof(double)); }
-    if (A.cover && keep_in) { if (m->t_cover.reserve(n * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "block scratch"); in(m->t_cover.p, A.cover, sizeof(double)); B.cover = (const double*)m->t_cover.p; }
-    if (A.dbg_d) { if (m->t_dd.reserve(n * 25 * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "block scratch"); B.dbg_d = (double*)m->t_dd.p; if (keep_in) in(B.dbg_d, A.dbg_d, 25 * sizeof(double)); }
-    if (A.dbg_a) { if (m->t_da.reserve(n * 16 * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "block scratch"); B.dbg_a = (double*)m->t_da.p; if (keep_in) in(B.dbg_a, A.dbg_a, 16 * sizeof(double)); }
-    if (A.dbg_n) { if (m->t_dn.reserve(n * sizeof(int))) return fail(UMPA_HIP_E_NOMEM, "block scratch"); B.dbg_n = (int*)m->t_dn.p; if (keep_in) in(B.dbg_n, A.dbg_n, sizeof(int)); }
+    if (r1 <= r0 || c1 <= c0) return 0;
+    const RegionArgs R = sub_region(A, r0, r1, c0, c1);
+    // the tiled kernels write this rectangle of the full arrays in place (row pitch = the full region's): nothing is
+    // copied, pixels below the coverage threshold keep what they had
+    if (tiled) return run_tiled(m, R, g, flags, s, 0, nullptr, sub);
+    // the general kernels take dense arrays: the rectangle is matched in scratch, gathered first because what the kernels
+    // may leave untouched (pixels below the coverage threshold) must come back as it was
+    const size_t n = (size_t)R.N0 * R.N1;
+    RegionArgs B = R;
+    B.pitch = B.N1;
+    B.v_k = B.v_px == 1 ? n : 1;                                      // planar values: planes of n
+    if (use_bufs(B, m->t, n)) return fail(UMPA_HIP_E_NOMEM, "block scratch");
+    hipError_t e = copy_maps(B, R, true, s);
     if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "block gather: %s", hipGetErrorString(e));
-    if (int rc = tiled ? run_tiled(m, B, g, flags, s, 0, nullptr, sub) : run_direct(m, B, s, flags)) return rc;
-    if (planar) for (int k = 0; k < np; k++) out(A.values + (size_t)k * nfull, B.values + (size_t)k * n, sizeof(double));
-    else out(A.values, B.values, np * sizeof(double));
-    out(A.err, B.err, sizeof(int));
-    if (A.uv) out(A.uv, B.uv, 2 * sizeof(double));
-    if (A.dbg_d) out(A.dbg_d, B.dbg_d, 25 * sizeof(double));
-    if (A.dbg_a) out(A.dbg_a, B.dbg_a, 16 * sizeof(double));
-    if (A.dbg_n) out(A.dbg_n, B.dbg_n, sizeof(int));
+    if (int rc = run_direct(m, B, s, flags)) return rc;
+    e = copy_maps(R, B, false, s);
     if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "block scatter: %s", hipGetErrorString(e));
     return 0;
 }
@@ -550,15 +554,13 @@ int run_block(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int r0,
 int run_stepping_cells(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int flags, hipStream_t s)
 {
     const int K = m->Na, pad = m->padding;
-    auto lo = [](int vmin, int org, int step, int N) { int q = vmin - org; q = q <= 0 ? 0 : (q + step - 1) / step; return std::min(q, N); };
-    auto hi = [](int vmax, int org, int step, int N) { int q = vmax - org; q = q < 0 ? 0 : q / step + 1; return std::min(q, N); };
     // per frame, in region pixel indices: rows [ra, rb) and columns [ca, cb) it contributes to; [ca, cs) = without the last column
     std::vector<int> ra(K), rb(K), ca(K), cb(K), cs(K), rcut{0, A.N0}, ccut{0, A.N1};
     for (int k = 0; k < K; k++) {
         const int pi = m->pos[2 * k], pj = m->pos[2 * k + 1], H = m->dims[2 * k], W = m->dims[2 * k + 1];
-        ra[k] = lo(pi + pad, A.org0, A.step0, A.N0); rb[k] = std::max(ra[k], hi(pi + H - pad, A.org0, A.step0, A.N0));
-        ca[k] = lo(pj + pad, A.org1, A.step1, A.N1); cb[k] = std::max(ca[k], hi(pj + W - pad, A.org1, A.step1, A.N1));
-        cs[k] = pair_slack(m) ? cb[k] : std::max(ca[k], std::min(cb[k], hi(pj + W - pad - 1, A.org1, A.step1, A.N1)));
+        ra[k] = index_lo(pi + pad, A.org0, A.step0, A.N0); rb[k] = std::max(ra[k], index_hi(pi + H - pad, A.org0, A.step0, A.N0));
+        ca[k] = index_lo(pj + pad, A.org1, A.step1, A.N1); cb[k] = std::max(ca[k], index_hi(pj + W - pad, A.org1, A.step1, A.N1));
+        cs[k] = pair_slack(m) ? cb[k] : std::max(ca[k], std::min(cb[k], index_hi(pj + W - pad - 1, A.org1, A.step1, A.N1)));
         rcut.push_back(ra[k]); rcut.push_back(rb[k]);
         ccut.push_back(ca[k]); ccut.push_back(cb[k]); ccut.push_back(cs[k]);
     }
@@ -585,23 +587,14 @@ int run_stepping_cells(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g
             if (!tile) { if (int rc = run_block(m, A, g, r0, r1, c0, c1, false, flags, s)) return rc; continue; }
             if ((int)S.size() == K) { if (int rc = run_block(m, A, g, r0, r1, c0, c1, true, flags, s)) return rc; continue; }   // every frame
             // this subset's descriptor list (a device slot per subset, uploaded when the frames' addresses have changed) and its box
-            std::vector<FrameDesc> h(S.size());
+            std::vector<FrameDesc> h;
+            for (int k : S) h.push_back(frame_desc(m, k));
             FrameSubset sub;
             sub.n = (int)S.size();
-            int br0 = 0, br1 = 1 << 30, bc0 = 0, bc1 = 1 << 30;
-            for (int q = 0; q < sub.n; q++) {
-                const int k = S[q];
-                memset(&h[q], 0, sizeof(FrameDesc));
-                h[q].sam = m->d_sam[k]; h[q].ref = m->d_ref[k]; h[q].mask = m->d_mask[k];
-                h[q].H = m->dims[2 * k]; h[q].W = m->dims[2 * k + 1]; h[q].pi = m->pos[2 * k]; h[q].pj = m->pos[2 * k + 1];
-                br0 = std::max(br0, h[q].pi); br1 = std::min(br1, h[q].pi + h[q].H - 1);
-                bc0 = std::max(bc0, h[q].pj); bc1 = std::min(bc1, h[q].pj + h[q].W - 1);
-            }
-            sub.box.r0 = br0; sub.box.r1 = br1; sub.box.c0 = bc0; sub.box.c1 = bc1; sub.box.Wf = m->dims[1]; sub.box.slack = g.box.slack;
+            sub.box = frame_box(h, m->dims[1], g.box.slack);
             umpa_hip_model::SubList& L = m->sub_lists[mask];
             if (!known) L.slot = (int)m->sub_lists.size() - 1;
             sub.frames = m->d_sub + (size_t)L.slot * K;
-            sub.host = nullptr;
             if (L.host.size() != h.size() || memcmp(L.host.data(), h.data(), h.size() * sizeof(FrameDesc)) != 0) {
                 L.host = h;                                          // the copy's source outlives the enqueue: the map's own storage
                 HIP_TRY(hipMemcpyAsync((void*)sub.frames, L.host.data(), L.host.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, s), UMPA_HIP_E_DEVICE);
@@ -661,10 +654,7 @@ int adopt_staged(umpa_hip_model* m, int flags, hipStream_t s)
     if (!m->h_desc) HIP_TRY(hipHostMalloc((void**)&m->h_desc, 2 * m->Na * sizeof(FrameDesc), hipHostMallocDefault), UMPA_HIP_E_NOMEM);
     static_assert(sizeof(FrameDesc) % 8 == 0, "descriptor layout");
     FrameDesc* h = m->h_desc + (m->d_sam[0] == (double*)m->d_back_blob ? m->Na : 0);   // one slot per buffer parity
-    for (int k = 0; k < m->Na; k++) {
-        h[k].sam = m->d_sam[k]; h[k].ref = m->d_ref[k]; h[k].mask = m->d_mask[k];
-        h[k].H = m->dims[2 * k]; h[k].W = m->dims[2 * k + 1]; h[k].pi = m->pos[2 * k]; h[k].pj = m->pos[2 * k + 1];
-    }
+    for (int k = 0; k < m->Na; k++) h[k] = frame_desc(m, k);
     HIP_TRY(hipMemcpyAsync(m->d_desc, h, m->Na * sizeof(FrameDesc), hipMemcpyHostToDevice, s), UMPA_HIP_E_DEVICE);
     m->staged = false;
     return 0;
@@ -733,14 +723,14 @@ umpa_hip_model* umpa_hip_create(int kind, int Na, const int* dims, double* const
             delete m;
             return nullptr;
         }
+        m->frame_total += (size_t)dims[2 * k] * dims[2 * k + 1];
     }
     bool ok = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking) == hipSuccess;
 
     m->d_sam.resize(Na); m->d_ref.resize(Na); m->d_mask.assign(Na, nullptr);
     if (ok && m->owns_frames) {
-        size_t total = 0;
-        for (int k = 0; k < Na; k++) total += (size_t)dims[2 * k] * dims[2 * k + 1];
+        const size_t total = m->frame_total;
         const size_t nstacks = m->has_mask ? 3 : 2;
         ok = hipMalloc(&m->d_frames_blob, total * nstacks * sizeof(double) + 16) == hipSuccess;     // (+16: pair_slack below)
         if (!ok) fail(UMPA_HIP_E_NOMEM, "cannot allocate %zu bytes for the frame stacks", total * nstacks * sizeof(double));
@@ -764,25 +754,19 @@ umpa_hip_model* umpa_hip_create(int kind, int Na, const int* dims, double* const
         for (int k = 0; k < Na; k++) { m->d_sam[k] = sam[k]; m->d_ref[k] = ref[k]; if (m->has_mask) m->d_mask[k] = mask[k]; }
     }
     if (ok) {
-        std::vector<FrameDesc> desc(Na);
-        for (int k = 0; k < Na; k++) {
-            desc[k].sam = m->d_sam[k]; desc[k].ref = m->d_ref[k]; desc[k].mask = m->d_mask[k];
-            desc[k].H = dims[2 * k]; desc[k].W = dims[2 * k + 1]; desc[k].pi = pos[2 * k]; desc[k].pj = pos[2 * k + 1];
-        }
+        const std::vector<FrameDesc> desc = frame_list(m);
         ok = hipMalloc((void**)&m->d_desc, Na * sizeof(FrameDesc)) == hipSuccess &&
              hipMemcpy(m->d_desc, desc.data(), Na * sizeof(FrameDesc), hipMemcpyHostToDevice) == hipSuccess;
         if (!ok) fail(UMPA_HIP_E_NOMEM, "cannot allocate the frame descriptor table");
     }
     if (ok) ok = upload_win(m, win, Nw) == 0;
-    if (ok && m->has_mask && m->owns_frames && !getenv("UMPA_HIP_NO_BINARY_MASKS")) {
+    if (ok && m->has_mask && m->owns_frames) {
         // 0/1 masks let corr_masked form the pair weight with one multiply; owned frames only (borrowed ones may change)
         int* d_flag = nullptr;
         int h_flag = 1;
-        size_t total = 0;
-        for (int k = 0; k < Na; k++) total += (size_t)dims[2 * k] * dims[2 * k + 1];
         if (hipMalloc((void**)&d_flag, sizeof(int)) == hipSuccess) {
             if (hipMemcpy(d_flag, &h_flag, sizeof(int), hipMemcpyHostToDevice) == hipSuccess) {
-                hipLaunchKernelGGL(umpa::mask_binary_kernel, dim3(2048), dim3(256), 0, m->stream, (const double*)m->d_mask[0], total, d_flag);
+                hipLaunchKernelGGL(umpa::mask_binary_kernel, dim3(2048), dim3(256), 0, m->stream, (const double*)m->d_mask[0], m->frame_total, d_flag);
                 if (hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
                     hipStreamSynchronize(m->stream) != hipSuccess) h_flag = 0;
                 m->mask_binary = h_flag == 1;
@@ -817,8 +801,7 @@ int umpa_hip_stage_sample(umpa_hip_model* m, const void* const* raw, int raw_dty
     if (raw_dtype < 0 || raw_dtype > 2) return fail(UMPA_HIP_E_ARG, "raw_dtype %d: 0 float64, 1 float32, 2 uint16", raw_dtype);
     HIP_TRY(hipSetDevice(m->device), UMPA_HIP_E_DEVICE);
     const size_t esz = raw_dtype == 0 ? 8 : raw_dtype == 1 ? 4 : 2;
-    size_t total = 0;
-    for (int k = 0; k < m->Na; k++) total += (size_t)m->dims[2 * k] * m->dims[2 * k + 1];
+    const size_t total = m->frame_total;
     if (!m->up_stream) HIP_TRY(hipStreamCreateWithFlags(&m->up_stream, hipStreamNonBlocking), UMPA_HIP_E_DEVICE);
     if (!m->ev_staged) HIP_TRY(hipEventCreateWithFlags(&m->ev_staged, hipEventDisableTiming), UMPA_HIP_E_DEVICE);
     if (!m->d_back_blob) {
@@ -913,12 +896,9 @@ void umpa_hip_destroy(umpa_hip_model* m)
     for (auto& l : m->launches) { (void)hipEventDestroy(l.t0); (void)hipEventDestroy(l.t1); }
     for (auto e : m->event_pool) (void)hipEventDestroy(e);
     tiled_release(m->tiled);
-    for (int q = 0; q < 2; q++) {
-        m->b_values[q].release(); m->b_uv[q].release(); m->b_err[q].release(); m->b_cover[q].release();
-        m->b_dd[q].release(); m->b_da[q].release(); m->b_dn[q].release();
-    }
+    for (MapBufs& b : m->b) b.release();
+    m->t.release();
     m->b_covout.release(); m->b_small.release(); m->b_kern.release();
-    m->t_values.release(); m->t_uv.release(); m->t_err.release(); m->t_cover.release(); m->t_dd.release(); m->t_da.release(); m->t_dn.release();
     if (m->d_desc) (void)hipFree(m->d_desc);
     if (m->d_sub) (void)hipFree(m->d_sub);
     if (m->d_win) (void)hipFree(m->d_win);
@@ -1031,21 +1011,21 @@ int umpa_hip_match_region(umpa_hip_model* m, int start0, int step0, int N0, int 
                           double* dbg_d, double* dbg_a, int* dbg_ncalls, int flags, void* stream)
 {
     if (!m || !values || !err) return fail(UMPA_HIP_E_ARG, "null argument");
-    if (nparam < (m->kind == 1 ? 5 : m->kind == 2 ? 7 : 4)) return fail(UMPA_HIP_E_ARG, "nparam=%d too small for this model", nparam);
+    if (nparam < kind_nparam(m->kind)) return fail(UMPA_HIP_E_ARG, "nparam=%d too small for this model", nparam);
     if (int rc = check_region(m, start0, step0, N0, start1, step1, N1)) return rc;
     HIP_TRY(hipSetDevice(m->device), UMPA_HIP_E_DEVICE);
     const size_t n = (size_t)N0 * N1;
 
-    RegionArgs A;
+    RegionArgs A{};
     A.org0 = m->padding + start0; A.step0 = step0; A.N0 = N0;       // model.pyx:482-483
     A.org1 = m->padding + start1; A.step1 = step1; A.N1 = N1; A.pitch = N1;
-    A.nparam = nparam; A.thr = cover_threshold; A.kern = nullptr; A.kern_stride = 0; A.row_base = 0; A.blur = nullptr; A.blur_F = 0; A.blur_ready = 0;
+    A.nparam = nparam; A.thr = cover_threshold;
     const bool planar = (flags & UMPA_HIP_F_PLANAR) != 0;
     A.v_px = planar ? 1 : (size_t)nparam; A.v_k = planar ? n : 1;
+    A.values = values; A.uv = uv; A.err = err; A.cover = covermap;
+    A.dbg_d = dbg_d; A.dbg_a = dbg_a; A.dbg_n = dbg_ncalls;
 
     if (flags & UMPA_HIP_F_DEVICE_IO) {
-        A.values = values; A.uv = uv; A.err = err; A.cover = covermap;
-        A.dbg_d = dbg_d; A.dbg_a = dbg_a; A.dbg_n = dbg_ncalls;
         if (int rc = adopt_staged(m, flags, (hipStream_t)stream)) return rc;
         if (m->rows_cb) {
             umpa_hip_rows_fn cb = m->rows_cb;
@@ -1064,39 +1044,24 @@ int umpa_hip_match_region(umpa_hip_model* m, int start0, int step0, int N0, int 
     const int os = m->out_set;                                        // this match's device output set
     m->out_set ^= 1;
     if (int rc = adopt_staged(m, flags, s)) return rc;
-    if (m->b_values[os].reserve(n * nparam * sizeof(double)) || m->b_err[os].reserve(n * sizeof(int)))
-        return fail(UMPA_HIP_E_NOMEM, "output buffers (%zu pixels)", n);
+    const RegionArgs H = A;                                           // the caller's host arrays
+    if (use_bufs(A, m->b[os], n)) return fail(UMPA_HIP_E_NOMEM, "output buffers (%zu pixels)", n);
     // values and err start from the caller's arrays (zeros in the reference, model.pyx:455,468).  They only matter
     // where the kernel reads them (DFKernel's a,b,c) or leaves them alone (pixels skipped by the coverage test):
-    // otherwise every element is overwritten and the upload is skipped.
-    if (m->kind == UMPA_HIP_KIND_DFKERNEL || covermap) {
-        HIP_TRY(hipMemcpyAsync(m->b_values[os].p, values, n * nparam * sizeof(double), hipMemcpyHostToDevice, s), UMPA_HIP_E_DEVICE);
-        HIP_TRY(hipMemcpyAsync(m->b_err[os].p, err, n * sizeof(int), hipMemcpyHostToDevice, s), UMPA_HIP_E_DEVICE);
-    }
-    A.values = (double*)m->b_values[os].p; A.err = (int*)m->b_err[os].p;
-    A.uv = nullptr; A.cover = nullptr; A.dbg_d = nullptr; A.dbg_a = nullptr; A.dbg_n = nullptr;
-    if (uv) {
-        if (m->b_uv[os].reserve(n * 2 * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "uv buffer");
-        HIP_TRY(hipMemcpyAsync(m->b_uv[os].p, uv, n * 2 * sizeof(double), hipMemcpyHostToDevice, s), UMPA_HIP_E_DEVICE);
-        A.uv = (double*)m->b_uv[os].p;
-    }
-    if (covermap) {
-        if (m->b_cover[os].reserve(n * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "coverage buffer");
-        HIP_TRY(hipMemcpyAsync(m->b_cover[os].p, covermap, n * sizeof(double), hipMemcpyHostToDevice, s), UMPA_HIP_E_DEVICE);
-        A.cover = (const double*)m->b_cover[os].p;
-    }
+    // otherwise every element is overwritten and the upload is skipped.  uv and cover are uploaded whenever given.
     // The debug maps are written for every pixel the kernels visit: they only need clearing where the coverage test
     // may skip pixels (1.4 GB of memset per C2 match otherwise).
-    const bool clear_dbg = covermap != nullptr;
-    if (dbg_d) { if (m->b_dd[os].reserve(n * 25 * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "debug_d buffer");
-                 if (clear_dbg) HIP_TRY(hipMemsetAsync(m->b_dd[os].p, 0, n * 25 * sizeof(double), s), UMPA_HIP_E_DEVICE);
-                 A.dbg_d = (double*)m->b_dd[os].p; }
-    if (dbg_a) { if (m->b_da[os].reserve(n * 16 * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "debug_a buffer");
-                 if (clear_dbg) HIP_TRY(hipMemsetAsync(m->b_da[os].p, 0, n * 16 * sizeof(double), s), UMPA_HIP_E_DEVICE);
-                 A.dbg_a = (double*)m->b_da[os].p; }
-    if (dbg_ncalls) { if (m->b_dn[os].reserve(n * sizeof(int))) return fail(UMPA_HIP_E_NOMEM, "debug_Ncalls buffer");
-                      if (clear_dbg) HIP_TRY(hipMemsetAsync(m->b_dn[os].p, 0, n * sizeof(int), s), UMPA_HIP_E_DEVICE);
-                      A.dbg_n = (int*)m->b_dn[os].p; }
+    const bool seeded = m->kind == UMPA_HIP_KIND_DFKERNEL || covermap;
+    hipError_t ue = hipSuccess;
+    for_each_map([&](int q, size_t per_px, int planes, auto* h, auto* d) {
+        const size_t bytes = n * per_px * planes * sizeof(*d);
+        if (!h || ue != hipSuccess) return;
+        if (q == MAP_UV || q == MAP_COVER || (seeded && (q == MAP_VALUES || q == MAP_ERR)))
+            ue = hipMemcpyAsync((void*)d, h, bytes, hipMemcpyHostToDevice, s);
+        else if (covermap && (q == MAP_DBG_D || q == MAP_DBG_A || q == MAP_DBG_N))
+            ue = hipMemsetAsync((void*)d, 0, bytes, s);
+    }, H, A);
+    if (ue != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "upload of the input maps: %s", hipGetErrorString(ue));
 
     // The region is matched in a few row chunks; all kernels are enqueued first (each chunk leaves an event on the
     // compute stream), then the rows of chunk c travel to the host on the copy stream while chunk c+1 is still
@@ -1113,7 +1078,6 @@ int umpa_hip_match_region(umpa_hip_model* m, int start0, int step0, int N0, int 
     // an asynchronous match overlaps its download with the NEXT match (two in flight): fewer, larger pieces are cheaper there
     // (step-scan series of 2048^2 x 5 frames: 8 pieces 4.09, 4: 3.86, 2: 3.76, 1: 3.79 ms per projection)
     if ((flags & UMPA_HIP_F_ASYNC) && pieces > 2) pieces = 2;
-    { static const char* pe = getenv("UMPA_HIP_PIECES"); if (pe && atoi(pe) > 0) pieces = atoi(pe); }   // tuning override
     const int N0d = step0 * (N0 - 1) + 1;
     const int piece_rows = pieces > 1 ? std::max(4 * UMPA_TILE, (N0d + pieces - 1) / pieces) : 0;
     if (int rc = run_match(m, A, flags, s, piece_rows, on_rows)) return rc;
@@ -1121,21 +1085,15 @@ int umpa_hip_match_region(umpa_hip_model* m, int start0, int step0, int N0, int 
 
     hipStream_t cs = m->copy_stream;
     hipError_t ce = hipSuccess;
-    auto down = [&](void* host, const void* dev, size_t elem_bytes, size_t per_px, int lo, int hi) {
-        if (ce != hipSuccess || !host) return;
-        const size_t off = (size_t)lo * N1 * per_px * elem_bytes, bytes = (size_t)(hi - lo) * N1 * per_px * elem_bytes;
-        ce = hipMemcpyAsync((char*)host + off, (const char*)dev + off, bytes, hipMemcpyDeviceToHost, cs);
-    };
     for (const Piece& p : piece_list) {
         if (p.done) { if (ce == hipSuccess) ce = hipStreamWaitEvent(cs, p.done, 0); }
         else if (ce == hipSuccess) ce = hipStreamSynchronize(s);
-        if (planar) for (int k = 0; k < nparam; k++) down(values + (size_t)k * n, A.values + (size_t)k * n, sizeof(double), 1, p.lo, p.hi);
-        else down(values, A.values, sizeof(double), nparam, p.lo, p.hi);
-        down(err, A.err, sizeof(int), 1, p.lo, p.hi);
-        down(uv, A.uv, sizeof(double), 2, p.lo, p.hi);
-        down(dbg_d, A.dbg_d, sizeof(double), 25, p.lo, p.hi);
-        down(dbg_a, A.dbg_a, sizeof(double), 16, p.lo, p.hi);
-        down(dbg_ncalls, A.dbg_n, sizeof(int), 1, p.lo, p.hi);
+        for_each_map([&](int q, size_t per_px, int planes, auto* h, auto* d) {      // rows [lo, hi) of every output map
+            const size_t row = (size_t)N1 * per_px * sizeof(*d);
+            for (int k = 0; h && q != MAP_COVER && k < planes && ce == hipSuccess; k++)
+                ce = hipMemcpyAsync((char*)(h + k * H.v_k) + p.lo * row, (const char*)(d + k * A.v_k) + p.lo * row,
+                                    (p.hi - p.lo) * row, hipMemcpyDeviceToHost, cs);
+        }, H, A);
     }
     if ((flags & UMPA_HIP_F_ASYNC) && ce == hipSuccess) {          // the caller collects the result with umpa_hip_wait
         umpa_hip_model::PendingMatch pm;
@@ -1157,7 +1115,7 @@ int umpa_hip_min(umpa_hip_model* m, int i, int j, double* values, double* uv, do
 {
     if (!m || !values) return fail(UMPA_HIP_E_ARG, "null argument");
     HIP_TRY(hipSetDevice(m->device), UMPA_HIP_E_DEVICE);
-    const int np = m->kind == 1 ? 5 : m->kind == 2 ? 7 : 4;
+    const int np = kind_nparam(m->kind);
     if (m->b_small.reserve(512 * sizeof(double))) return fail(UMPA_HIP_E_NOMEM, "scratch");
     double* d = (double*)m->b_small.p;                 // [0..7) values, [8..9] uv, [10] err(int), [11] ncalls(int), [12..37) d, [37..53) a
     double h[53];
@@ -1166,10 +1124,10 @@ int umpa_hip_min(umpa_hip_model* m, int i, int j, double* values, double* uv, do
     if (uv) { h[8] = uv[0]; h[9] = uv[1]; }
     hipStream_t s = m->stream;
     HIP_TRY(hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, s), UMPA_HIP_E_DEVICE);
-    RegionArgs A;
+    RegionArgs A{};
     A.org0 = i; A.step0 = 1; A.N0 = 1; A.org1 = j; A.step1 = 1; A.N1 = 1; A.pitch = 1;      // Model::min takes absolute coordinates
-    A.values = d; A.nparam = np; A.v_px = np; A.v_k = 1; A.uv = d + 8; A.err = (int*)(d + 10); A.cover = nullptr; A.thr = 0.0;
-    A.dbg_n = (int*)(d + 11); A.dbg_d = d + 12; A.dbg_a = d + 37; A.kern = nullptr; A.kern_stride = 0; A.row_base = 0; A.blur = nullptr; A.blur_F = 0; A.blur_ready = 0;
+    A.values = d; A.nparam = np; A.v_px = np; A.v_k = 1; A.uv = d + 8; A.err = (int*)(d + 10);
+    A.dbg_n = (int*)(d + 11); A.dbg_d = d + 12; A.dbg_a = d + 37;
     if (int rc = run_direct(m, A, s)) return rc;
     HIP_TRY(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s), UMPA_HIP_E_DEVICE);
     HIP_TRY(hipStreamSynchronize(s), UMPA_HIP_E_DEVICE);
