@@ -1,7 +1,7 @@
 // umpa_direct.h -- the general ("direct") matching kernel: one lane per output pixel, the
 // windowed multi-frame cost evaluated by an explicit window x frame sum straight from the
 // frames in HBM/L2, exactly the arithmetic of the reference cost functions
-// (UMPA/lib/Model.cpp:359-509 NoDF, :631-862 DF), including masks, per-frame positions
+// (UMPA/lib/Model.cpp:359-509 NoDF, :631-862 DF; the pieces shared with the other paths: umpa_cost.h), including masks, per-frame positions
 // (sample stepping), unequal frame shapes and both coordinate conventions.
 //
 // It is the path for everything the tiled fast path (umpa_tiled.h) does not cover, and the
@@ -10,7 +10,7 @@
 // diverges.  Window weights and frame descriptors are wave-uniform and come in through
 // scalar loads.
 #pragma once
-#include "umpa_walk.h"
+#include "umpa_cost.h"
 
 namespace umpa {
 
@@ -63,11 +63,6 @@ __device__ __forceinline__ FrameDesc load_frame(const FrameDesc* frames, int k)
     f.sam = g->sam; f.ref = g->ref; f.mask = g->mask;
     f.H = g->H; f.W = g->W; f.pi = g->pi; f.pj = g->pj;
     return f;
-}
-
-__device__ __forceinline__ double pair_weight(double a, double b)   // Utils.cpp:125-130
-{
-    return a * b * fast_rcp(a + b + 1e-8);       // one division per window element and frame: the reciprocal is what the masked kernels spend their time on
 }
 
 #define UMPA_BLUR_HALF 8                                   // Model.h:7 KERNEL_WINDOW_SIZE
@@ -125,7 +120,7 @@ __device__ inline void blur_footprint(const ModelDev& m, int i, int j, const UMP
     for (int k = 0; k < m.Na; k++) {
         const FrameDesc f = load_frame(m.frames, k);
         const int li = i - f.pi, lj = j - f.pj;
-        if (li - pad < 0 || li + pad > f.H || lj - pad < 0 || lj + pad > f.W) continue;     // frame does not contribute here
+        if (frame_misses(f.H, f.W, li, lj, pad)) continue;
         UMPA_GLOBAL double* out = blur + (size_t)k * F * F * stride;
         const UMPA_GLOBAL double* img = gp(f.ref);
         const UMPA_GLOBAL double* wgt = gp(f.mask);
@@ -226,7 +221,7 @@ blur_tiles_kernel(ModelDev m, RegionArgs A, BlurTileGeom G)
         }
         __syncthreads();
         const int li = i - f.pi, lj = j - f.pj;
-        if (!wanted || li - pad < 0 || li + pad > f.H || lj - pad < 0 || lj + pad > f.W) continue;   // frame does not contribute here
+        if (!wanted || li - pad < 0 || li + pad > f.H || lj - pad < 0 || lj + pad > f.W) continue;   // (frame_misses as a call changes both kernels)
         UMPA_GLOBAL double* out = blur + (size_t)k * F * F * stride;
         // this pixel's footprint origin inside the patch: footprint (fy, fx), tap (a, b) reads patch (r0 + fy + a, c0 + fx + b)
         const int r0 = ty * A.step0, c0 = tx * A.step1;
@@ -278,8 +273,9 @@ __device__ __forceinline__ int eval_direct(const ModelDev& m, int i, int j, int 
                                            const UMPA_GLOBAL double* kern = nullptr, size_t kstride = 0,
                                            const UMPA_GLOBAL double* blur = nullptr, int blur_F = 0)
 {
+    // shift_status (Model.cpp:372-399 / :654-681), kept as three exits: as a call the status is a chain of selects and match_direct<2, true, 6..8>,
+    // at the 168-VGPR cap, spill 133 / 153 / 153 -> 134 / 158 / 159 VGPRs (profiles/r06_cost_refactor.txt)
     const int ms = m.ms;
-    // Model.cpp:372-399 / :654-681 (flags are asymmetric in the reference; kept)
     if (si <= -ms || si >= ms) return UMPA_ST_BOUND;
     if (sj <= -ms) return UMPA_ST_BOUND | UMPA_ST_DIM;
     if (sj >= ms) return UMPA_ST_BOUND | UMPA_ST_DIM | UMPA_ST_POSITIVE;
@@ -294,7 +290,7 @@ __device__ __forceinline__ int eval_direct(const ModelDev& m, int i, int j, int 
     for (int k = 0; k < m.Na; k++) {
         const FrameDesc f = load_frame(m.frames, k);
         const int li = i - f.pi, lj = j - f.pj;          // Model.cpp:430-433 / :716-719
-        if (li - pad < 0 || li + pad > f.H || lj - pad < 0 || lj + pad > f.W) continue;
+        if (frame_misses(f.H, f.W, li, lj, pad)) continue;
         const size_t ro = (size_t)(ri - f.pi - Nw) * f.W + (rj - f.pj - Nw);
         const size_t qo = (size_t)(qi - f.pi - Nw) * f.W + (qj - f.pj - Nw);
         const UMPA_GLOBAL double* __restrict__ R = gp(f.ref) + ro;
@@ -537,7 +533,7 @@ match_staged_kernel(ModelDev m, RegionArgs A, int nbx, int nby, StagedGeom G)
     while (__syncthreads_count(w.phase < PH_FIT) >= UMPA_STAGED_TAIL) {
         const bool ev = w.phase < PH_FIT;
         const int si = w.req_i, sj = w.req_j;
-        int st = UMPA_ST_OK;                                         // Model.cpp:372-399 / :654-681
+        int st = UMPA_ST_OK;                                         // Model.cpp:372-399 / :654-681; written out, as the cover test below: as calls they change all 18 match_staged kernels
         if (si <= -ms || si >= ms) st = UMPA_ST_BOUND;
         else if (sj <= -ms) st = UMPA_ST_BOUND | UMPA_ST_DIM;
         else if (sj >= ms) st = UMPA_ST_BOUND | UMPA_ST_DIM | UMPA_ST_POSITIVE;
@@ -702,7 +698,7 @@ __global__ void coverage_kernel(ModelDev m, int org0, int step0, int N0, int org
     for (int k = 0; k < m.Na; k++) {
         const FrameDesc f = load_frame(m.frames, k);
         const int li = i - f.pi, lj = j - f.pj;
-        if (li - pad < 0 || li + pad > f.H || lj - pad < 0 || lj + pad > f.W) continue;
+        if (frame_misses(f.H, f.W, li, lj, pad)) continue;
         c += has_mask ? gp(f.mask)[(size_t)li * f.W + lj] : 1.0;
     }
     gpw(out)[(size_t)xi * N1 + xj] = c;

@@ -104,16 +104,6 @@ mask_binary_kernel(const double* __restrict__ mask, size_t n, int* flag)
     if (!ok) *flag = 0;
 }
 
-// combine_weights (Utils.cpp:125-130) with v_rcp_f64 and ONE Newton step (relative error ~1e-14; the weight enters
-// every sum linearly and identically, so this is a 1e-14 perturbation of the window, not of a cancellation)
-__device__ __forceinline__ double pair_weight_fast(double a, double b)
-{
-    const double d = a + b + 1e-8;
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    return a * b * r;
-}
-
 // fir_block (umpa_corr.h) with the inputs consumed as they arrive: fewer values live (corr_masked is short of registers)
 template <int NW, int CB>
 __device__ __forceinline__ void fir_stream(const double* __restrict__ in, int stride, const double* h, double* out)
@@ -417,7 +407,7 @@ __device__ __forceinline__ void corr_masked_tile(const ModelDev& m, const Masked
                 if (KIND == 1) {
                     const double t2 = sums[3 * NPX + px], ma = sums[4 * NPX + px], mb = sums[5 * NPX + px], wt = sums[6 * NPX + px];
                     const double t4 = A.sigma > 0 ? ma : mb, t6 = A.sigma > 0 ? mb : ma;
-                    const double det = t2 * t3 - t6 * t6;               // Model.cpp:849-858
+                    const double det = t2 * t3 - t6 * t6;               // Model.cpp:849-858, as eval_direct (a shared helper changes the 16 dark-field kernels)
                     const double Kc = (t2 * t5 - t4 * t6) / det;
                     const double beta = (t3 * t4 - t5 * t6) / det;
                     const double T = beta + Kc;
@@ -510,7 +500,7 @@ replay_cost_kernel(ModelDev m, const double* table, size_t slot_stride, int drow
             double c = 0.0;
             Fit fit = w.live;
             const int si = w.req_i, sj = w.req_j;
-            int st = UMPA_ST_OK;
+            int st = UMPA_ST_OK;                                        // (shift_status as a call changes both replay_cost kernels)
             if (si <= -ms || si >= ms) st = UMPA_ST_BOUND;
             else if (sj <= -ms) st = UMPA_ST_BOUND | UMPA_ST_DIM;
             else if (sj >= ms) st = UMPA_ST_BOUND | UMPA_ST_DIM | UMPA_ST_POSITIVE;

@@ -20,7 +20,8 @@
 //                 This is the dominant kernel (fp64 FMA / LDS bound).
 //   replay_walk : one lane per pixel replays the reference's walk (umpa_walk.h) with every
 //                 cost evaluation replaced by a table lookup + the closed-form solve of
-//                 Model.cpp:849-858, so err / Ncalls / integer minimum stay bit-identical.
+//                 Model.cpp:849-858 (solve_rcp, umpa_cost.h), so err / Ncalls / integer minimum
+//                 stay bit-identical.
 //
 // LDS tiles are stored transposed ([column][row], row stride odd) so that lanes that walk
 // along rows read and write consecutive 8-byte words (no bank conflicts for ds_read_b64).
@@ -238,6 +239,13 @@ struct PixConst { double t1, t3, t2, t6; };
 // has in registers anyway: W[r_k] = mean_k * sum(w) by the definition of the mean (Model.cpp:739), so t6 = sum(w) t2.
 // (Two map planes and two cache-line streams per evaluation less than reading them back.)
 
+// Where the lookup of shift (si, sj), |si|, |sj| < ms, reads: its slot of replay_walk's table (the masked table's writer
+// and reader, umpa_masked.h, keep their own) and the sample / reference window positions in the maps (Model.cpp:688-701).
+// (Scalars by value: through references or a struct every replay_walk changes, profiles/r06_cost_refactor.txt.)
+__device__ __forceinline__ unsigned table_slot(int ms, int si, int sj) { const int UJ = 2 * ms - 1; return (unsigned)((si + ms - 1) * UJ + (sj + ms - 1)); }
+__device__ __forceinline__ size_t sample_at(int W, int ref_mode, int i, int j, int si, int sj) { return ref_mode ? (size_t)(i - si) * W + (j - sj) : (size_t)i * W + j; }
+__device__ __forceinline__ size_t reference_at(int W, int ref_mode, int i, int j, int si, int sj) { return ref_mode ? (size_t)i * W + j : (size_t)(i + si) * W + (j + sj); }
+
 // NA > 0: the number of frames is a compile-time constant (<= UMPA_KTEMPL) and every map plane is addressable
 // with 32-bit byte offsets: straight-line code, no per-frame tests.  NA == 0: any frame count.
 template <int KIND, int NA>
@@ -245,28 +253,22 @@ __device__ __forceinline__ int eval_lookup(const ModelDev& m, const Maps& M, con
                                            int i, int j, size_t tpx, int si, int sj,
                                            const double* fixed, const PixConst& pc, double& cost, Fit& fit)
 {
-    // (no implicit contraction: a * b + c stays two roundings unless written as fma().  Left to the compiler, the inlined
-    //  copies of this arithmetic -- here, in lookup_solve, in every kernel variant -- may be fused differently from one another:
-    //  seen in round 4 when a restructured replay_walk answered T an ulp away from the on-demand kernel's on 27 k pixels)
-#pragma clang fp contract(off)
+    // shift_status, kept as three exits: as a call it changes 41 of the 52 replay_walk kernels and the on-demand ones at the
+    // 168-VGPR cap spill more (<1, 21..24, true>: 10 / 19 / 51 / 45 -> 16 / 27 / 52 / 52 VGPRs; profiles/r06_cost_refactor.txt)
     const int ms = m.ms;
     if (si <= -ms || si >= ms) return UMPA_ST_BOUND;
     if (sj <= -ms) return UMPA_ST_BOUND | UMPA_ST_DIM;
     if (sj >= ms) return UMPA_ST_BOUND | UMPA_ST_DIM | UMPA_ST_POSITIVE;
-    const int UJ = 2 * ms - 1;
-    const unsigned slot = (unsigned)((si + ms - 1) * UJ + (sj + ms - 1));
     // slot_stride < 2^32 (tiled_match bounds the row chunk): one 32x32->64-bit multiply-add
     // (a non-temporal load here is slower: 1.25 -> 1.32 ms on C2)
-    const double t5 = gp(R.table)[(size_t)slot * (unsigned)R.slot_stride + tpx];
-    // window positions (Model.cpp:688-701)
-    const size_t xs = ref_mode ? (size_t)(i - si) * M.W + (j - sj) : (size_t)i * M.W + j;
-    const size_t xr = ref_mode ? (size_t)i * M.W + j : (size_t)(i + si) * M.W + (j + sj);
+    const double t5 = gp(R.table)[(size_t)table_slot(ms, si, sj) * (unsigned)R.slot_stride + tpx];
+    const size_t xs = sample_at(M.W, ref_mode, i, j, si, sj), xr = reference_at(M.W, ref_mode, i, j, si, sj);
     const double rwt = 1.0 / (double)m.Nwt;                         // wave-uniform: scalar
     double t1 = pc.t1, t3 = pc.t3;
     if (ref_mode) t1 = NA > 0 ? ld_off(gp(M.SamSq), (unsigned)xs * 8u) : gp(M.SamSq)[xs];
     else t3 = NA > 0 ? ld_off(gp(M.RefSq), (unsigned)xr * 8u) : gp(M.RefSq)[xr];
     if (KIND == 1) {
-        double t2 = 0.0, t4 = 0.0;
+        double t2 = 0.0, t4 = 0.0;                                  // declared here, t6 below, solve_rcp per branch: hoisted, replay_walk's code changes
         const size_t plane = (size_t)M.H * M.W;
         if (NA > 0) {
             const unsigned bm = (unsigned)(ref_mode ? xs : xr) * 16u;
@@ -293,34 +295,14 @@ __device__ __forceinline__ int eval_lookup(const ModelDev& m, const Maps& M, con
         double t6;
         if (ref_mode) { t2 = pc.t2; t6 = pc.t6; }                   // the moving maps were the sample's: the means are the pixel's own
         else t6 = m.win_sum * t2;
-        // Model.cpp:849-858 with one reciprocal instead of the reference's three divisions by the same
-        // determinant and the division by wt (1-ulp level differences; the bar is 1e-5).  The dark-field
-        // value v = K/T is only needed for the pixel's final answer: `fit.v` carries K, replay_walk divides once.
-        const double rdet = fast_rcp(t2 * t3 - t6 * t6);
-        const double K = (t2 * t5 - t4 * t6) * rdet;
-        const double beta = (t3 * t4 - t5 * t6) * rdet;
-        fit.t = beta + K;
-        fit.v = K;
-        cost = (t1 + beta * beta * t2 + K * K * t3 - 2 * beta * t4 - 2 * K * t5 + 2 * beta * K * t6) * rwt;
-    } else {
-        fit.t = t5 / t3;                                            // Model.cpp:502-505
-        fit.v = 0.0;
-        cost = (t1 - t5 * fit.t) * rwt;
-    }
+        solve_rcp<KIND>(t1, t2, t3, t4, t5, t6, rwt, cost, fit);
+    } else solve_rcp<KIND>(t1, 0.0, t3, 0.0, t5, 0.0, rwt, cost, fit);
     return UMPA_ST_OK;
 }
 
-// The same evaluation in three pieces for the frame-count templates (NA > 0), so that a caller can have the loads of TWO
-// evaluations in flight before it waits for either (replay_walk's speculative second lookup): status, loads, solve.
-// lookup_solve repeats eval_lookup's arithmetic expression by expression: the numbers are the same.
-__device__ __forceinline__ int lookup_status(int ms, int si, int sj)
-{
-    if (si <= -ms || si >= ms) return UMPA_ST_BOUND;
-    if (sj <= -ms) return UMPA_ST_BOUND | UMPA_ST_DIM;
-    if (sj >= ms) return UMPA_ST_BOUND | UMPA_ST_DIM | UMPA_ST_POSITIVE;
-    return UMPA_ST_OK;
-}
-
+// The same evaluation in pieces for the frame-count templates (NA > 0), so that a caller can have the loads of TWO
+// evaluations in flight before it waits for either (replay_walk's speculative second lookup): shift_status, the loads, the
+// solve.  Addresses (table_slot, sample_at, reference_at) and arithmetic (solve_rcp) are eval_lookup's own.
 template <int NA>
 struct LookupRaw {
     double t5, sq;                                                  // table entry; SamSq ('ref' mode) or RefSq at the moving window
@@ -331,11 +313,8 @@ template <int KIND, int NA>
 __device__ __forceinline__ void lookup_load(const ModelDev& m, const Maps& M, const ReplayArgs& R, int ref_mode,
                                             int i, int j, size_t tpx, int si, int sj, LookupRaw<NA>& raw)   // |si|, |sj| < ms
 {
-    const int ms = m.ms, UJ = 2 * ms - 1;
-    const unsigned slot = (unsigned)((si + ms - 1) * UJ + (sj + ms - 1));
-    raw.t5 = gp(R.table)[(size_t)slot * (unsigned)R.slot_stride + tpx];
-    const size_t xs = ref_mode ? (size_t)(i - si) * M.W + (j - sj) : (size_t)i * M.W + j;
-    const size_t xr = ref_mode ? (size_t)i * M.W + j : (size_t)(i + si) * M.W + (j + sj);
+    raw.t5 = gp(R.table)[(size_t)table_slot(m.ms, si, sj) * (unsigned)R.slot_stride + tpx];
+    const size_t xs = sample_at(M.W, ref_mode, i, j, si, sj), xr = reference_at(M.W, ref_mode, i, j, si, sj);
     raw.sq = ref_mode ? ld_off(gp(M.SamSq), (unsigned)xs * 8u) : ld_off(gp(M.RefSq), (unsigned)xr * 8u);
     if (KIND == 1) {
         const size_t plane = (size_t)M.H * M.W;
@@ -350,29 +329,16 @@ template <int KIND, int NA>
 __device__ __forceinline__ void lookup_solve(const ModelDev& m, int ref_mode, const LookupRaw<NA>& raw,
                                              const double* fixed, const PixConst& pc, double& cost, Fit& fit)
 {
-#pragma clang fp contract(off)                                      // (as eval_lookup: the same roundings in every inlined copy)
-    const double t5 = raw.t5;
     const double rwt = 1.0 / (double)m.Nwt;
-    double t1 = pc.t1, t3 = pc.t3;
+    double t1 = pc.t1, t3 = pc.t3, t6 = 0.0, t2 = 0.0, t4 = 0.0;    // t6 before t2: any other order changes replay_walk<1, 1..11, false>
     if (ref_mode) t1 = raw.sq; else t3 = raw.sq;
     if (KIND == 1) {
-        double t2 = 0.0, t4 = 0.0;
 #pragma unroll
         for (int k = 0; k < NA; k++) { const double a = raw.mp[k >> 1][k & 1]; t4 = fma(a, fixed[k], t4); t2 = fma(a, a, t2); }
-        double t6;
         if (ref_mode) { t2 = pc.t2; t6 = pc.t6; }
         else t6 = m.win_sum * t2;
-        const double rdet = fast_rcp(t2 * t3 - t6 * t6);
-        const double K = (t2 * t5 - t4 * t6) * rdet;
-        const double beta = (t3 * t4 - t5 * t6) * rdet;
-        fit.t = beta + K;
-        fit.v = K;
-        cost = (t1 + beta * beta * t2 + K * K * t3 - 2 * beta * t4 - 2 * K * t5 + 2 * beta * K * t6) * rwt;
-    } else {
-        fit.t = t5 / t3;
-        fit.v = 0.0;
-        cost = (t1 - t5 * fit.t) * rwt;
     }
+    solve_rcp<KIND>(t1, t2, t3, t4, raw.t5, t6, rwt, cost, fit);
 }
 
 // Workgroup = UMPA_REPLAY_ROWS waves, each on a block of 64 pixels (ReplayArgs::bw_log2: 16 x 4, or 32 x 2 on corr_march's table; the
@@ -498,7 +464,7 @@ replay_walk_kernel(ModelDev m, Maps M, ReplayArgs R, RegionArgs A, OdArgs od_in)
             // range loads shift (0, 0) and is answered by its status alone.
             int si = w.req_i, sj = w.req_j;
             const bool spec = walk_speculate(w, si, sj);
-            const int st = lookup_status(m.ms, w.req_i, w.req_j), st2 = lookup_status(m.ms, si, sj);
+            const int st = shift_status(m.ms, w.req_i, w.req_j), st2 = shift_status(m.ms, si, sj);
             const bool ok1 = st == UMPA_ST_OK, ok2 = st2 == UMPA_ST_OK;
             LookupRaw<NA> r1, r2;
             lookup_load<KIND, NA>(m, M, R, m.ref_mode, i, j, tpx, ok1 ? w.req_i : 0, ok1 ? w.req_j : 0, r1);
