@@ -1,0 +1,57 @@
+/*
+ * umpa_grid.h -- exhaustive grid search and the cost volume (libumpa_grid.so, gfx950).
+ *
+ * The tiled fast path of libumpa_hip.so computes the windowed cost's correlation term for EVERY integer shift of the
+ * search box at every pixel (the exhaustive table).  The default minimiser, the reference's walk,
+ * reads about 18 of its entries per pixel.  This library reads all of them:
+ *
+ *   umpa_grid_match_region  the global minimum over the (2 max_shift - 1)^2 integer shifts of every pixel, followed by
+ *                           the walk's own sub-pixel step on the 4x4 neighbourhood of that minimum;
+ *   umpa_grid_cost_volume   the cost (and optionally transmission and dark-field) of every shift at every pixel.
+ *
+ * Both work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
+ * one shape at position (0, 0), steps and search ranges within that path's limits.  Anything else fails with
+ * UMPA_HIP_E_UNSUPPORTED before a kernel is launched.  Models are created, configured and destroyed through
+ * include/umpa_hip.h; link both libraries.  Error text: umpa_hip_last_error() for codes that umpa_hip_match_region
+ * produced, umpa_grid_last_error() for this library's own.
+ */
+#ifndef UMPA_GRID_H
+#define UMPA_GRID_H
+
+#include "umpa_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The arguments, flags (UMPA_HIP_F_DEVICE_IO, _PLANAR, _REUSE_REF_MAPS, _USE_STAGED, _ASYNC), chunked downloads and the
+ * rows callback of umpa_hip_match_region.  `uv` must be NULL (start shifts mean nothing to an exhaustive search:
+ * UMPA_HIP_E_ARG).  Per pixel:
+ *   the integer minimum is the first shift, rows first then columns, whose cost is strictly below every earlier one
+ *   (a NaN cost never wins);
+ *   err = 1: the quadrant rule of the walk applied to the four neighbours of the minimum picks the 4x4 neighbourhood;
+ *     dx, dy, f come from the sub-pixel fit the model is set to (mode 0: the integer minimum, f = 1 - ip as in the
+ *     reference); T (and df) are those of the integer minimum; dbg_ncalls = (2 max_shift - 1)^2; dbg_a is the 4x4
+ *     neighbourhood, dbg_d the 5x5 one around the minimum with -1 outside the search range;
+ *   err = 0 where that 4x4 neighbourhood leaves the search range: dx, dy are the integer minimum, f its cost, T (df) its
+ *     fit; dbg_a is zero;
+ *   err = 0 and zeros (dbg_d: -1) where no shift has a finite cost.
+ */
+int umpa_grid_match_region(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
+                           double *values, int nparam, double *uv, int *err,
+                           const double *covermap, double cover_threshold,
+                           double *dbg_d, double *dbg_a, int *dbg_ncalls, int flags, void *stream);
+
+/* cost[(si + max_shift - 1) * U + (sj + max_shift - 1)][xi][xj], U = 2 max_shift - 1, for the region's N0 x N1 pixels
+ * (si: row shift, sj: column shift); `T` and `df` (dark-field model only) in the same layout, each may be NULL.
+ * Host arrays, or device arrays with UMPA_HIP_F_DEVICE_IO (the call then only enqueues work on `stream`); no other flag.
+ * An array holds U * U * N0 * N1 doubles. */
+int umpa_grid_cost_volume(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
+                          double *cost, double *T, double *df, int flags, void *stream);
+
+const char *umpa_grid_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* UMPA_GRID_H */

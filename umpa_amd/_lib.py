@@ -139,6 +139,52 @@ def hip():
     return _hip
 
 
+GRID_LIB_PATH = os.path.join(_HERE, "libumpa_grid.so")
+# every symbol include/umpa_grid.h declares
+GRID_SYMBOLS = ["match_region", "cost_volume", "last_error"]
+_grid = None
+
+
+class GridNative:
+    """``libumpa_grid.so`` (``include/umpa_grid.h``): the exhaustive grid search and the cost volume, on models of
+    ``libumpa_hip.so``."""
+
+    def __init__(self, path):
+        if not os.path.exists(path):
+            raise NativeError(
+                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(there is no CPU fallback)" % path)
+        self.path = path
+        self.lib = C.CDLL(path)
+        mr = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self.match_region = self._f("match_region", C.c_int, mr)
+        self.cost_volume = self._f("cost_volume", C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p])
+        self.last_error = self._f("last_error", C.c_char_p, [])
+
+    def _f(self, name, restype, argtypes):
+        fn = getattr(self.lib, "umpa_grid_" + name)
+        fn.restype, fn.argtypes = restype, argtypes
+        return fn
+
+    def error(self):
+        return (self.last_error() or b"").decode()
+
+    def check(self, rc, what):
+        if rc is not None and rc < 0:
+            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
+        return rc
+
+
+def grid():
+    """The grid-search library, loaded at first use (after the product library it works on).  Raises if it is not built."""
+    global _grid
+    if _grid is None:
+        hip()
+        _grid = GridNative(GRID_LIB_PATH)
+    return _grid
+
+
 ROWS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)       # umpa_hip_rows_fn
 
 

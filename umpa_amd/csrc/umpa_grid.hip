@@ -1,0 +1,152 @@
+// umpa_grid.hip -- libumpa_grid.so: exhaustive grid search and the cost volume (include/umpa_grid.h).  gfx950 only.
+//
+// A second library, built from the headers of libumpa_hip.so by the same build: it holds the two kernel families of
+// umpa_grid_kernels.h and no other feature code.  A call sets itself as the model's table consumer (umpa_hipx.h), runs
+// umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
+// therefore the existing ones -- and clears the consumer again.  No CPU fallback.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstdarg>
+#include <cstring>
+#include <string>
+
+#include "../../include/umpa_grid.h"
+#include "umpa_hipx.h"
+#include "umpa_grid_kernels.h"
+
+using namespace umpa;
+
+#define UMPA_GRID_API extern "C" __attribute__((visibility("default")))
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+struct GridJob {
+    bool volume = false;              // cost_volume_kernel instead of grid_min_kernel
+    VolumeArgs V = {nullptr, nullptr, nullptr, 0};
+    // host-array cost volume: device copies of the wanted arrays (cost, T, df), allocated at the first chunk (the model's
+    // search range is known there)
+    bool host = false, want[3] = {false, false, false};
+    double* dev[3] = {nullptr, nullptr, nullptr};
+    size_t count = 0;                 // doubles per array
+    const char* refused = nullptr;
+};
+
+// the frame count as a template constant exactly where replay_walk's dispatch has it (tiled_match)
+template <int KIND, int NA>
+void launch(const GridJob& J, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
+{
+    if (J.volume) {
+        hipLaunchKernelGGL((cost_volume_kernel<KIND, NA>), dim3((A.N1 + 63) / 64, R.rows), dim3(64), 0, s, dev, M, R, A, J.V);
+    } else {
+        const int bw = 1 << R.bw_log2, bh = 64 >> R.bw_log2;
+        hipLaunchKernelGGL((grid_min_kernel<KIND, NA>), dim3((A.N1 + bw - 1) / bw, (R.rows + bh - 1) / bh), dim3(64), 0, s, dev, M, R, A);
+    }
+}
+
+hipError_t consumer(void* user, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
+{
+    GridJob& J = *(GridJob*)user;
+    const int kind = M.WS ? 1 : 0;
+    if (J.volume) {
+        if (J.want[2] && kind != 1) { J.refused = "a dark-field volume needs the dark-field model"; return hipErrorInvalidValue; }
+        const int U = 2 * dev.ms - 1;
+        J.V.plane = (size_t)A.N0 * A.N1;
+        if (J.host && J.count == 0) {
+            J.count = (size_t)U * U * J.V.plane;
+            for (int q = 0; q < 3; q++)
+                if (J.want[q] && hipMalloc((void**)&J.dev[q], J.count * sizeof(double)) != hipSuccess) { J.dev[q] = nullptr; return hipErrorOutOfMemory; }
+            J.V.cost = J.dev[0]; J.V.T = J.dev[1]; J.V.df = J.dev[2];
+        }
+    }
+    if (R.rows <= 0 || A.N1 <= 0) return hipSuccess;
+    const bool small = (size_t)M.H * M.W * 2 * sizeof(double) < ((size_t)1 << 32);   // a pair plane (tiled_match)
+#define UMPA_GRID_NA(n) case n: launch<1, n>(J, dev, M, R, A, s); break;
+    if (kind == 1 && small && dev.Na <= UMPA_KTEMPL) {
+        switch (dev.Na) {
+            UMPA_GRID_NA(1) UMPA_GRID_NA(2) UMPA_GRID_NA(3) UMPA_GRID_NA(4) UMPA_GRID_NA(5) UMPA_GRID_NA(6)
+            UMPA_GRID_NA(7) UMPA_GRID_NA(8) UMPA_GRID_NA(9) UMPA_GRID_NA(10) UMPA_GRID_NA(11) UMPA_GRID_NA(12)
+            UMPA_GRID_NA(13) UMPA_GRID_NA(14) UMPA_GRID_NA(15) UMPA_GRID_NA(16) UMPA_GRID_NA(17) UMPA_GRID_NA(18)
+            UMPA_GRID_NA(19) UMPA_GRID_NA(20) UMPA_GRID_NA(21) UMPA_GRID_NA(22) UMPA_GRID_NA(23) UMPA_GRID_NA(24)
+        }
+    } else if (kind == 1) launch<1, 0>(J, dev, M, R, A, s);
+    else launch<0, 0>(J, dev, M, R, A, s);
+#undef UMPA_GRID_NA
+    return hipGetLastError();
+}
+
+// umpa_hip_match_region down the tiled path with `J` as the model's table consumer; the consumer is cleared whatever happens
+int run(umpa_hip_model* m, GridJob& J, int start0, int step0, int N0, int start1, int step1, int N1,
+        double* values, int nparam, int* err, const double* covermap, double thr,
+        double* dbg_d, double* dbg_a, int* dbg_n, int flags, void* stream)
+{
+    if (int rc = umpa_hipx_set_table_consumer(m, consumer, &J)) return fail(rc, "%s", umpa_hip_last_error());
+    const int rc = umpa_hip_match_region(m, start0, step0, N0, start1, step1, N1, values, nparam, nullptr, err, covermap, thr,
+                                         dbg_d, dbg_a, dbg_n, flags | UMPA_HIP_F_FORCE_TILED, stream);
+    (void)umpa_hipx_set_table_consumer(m, nullptr, nullptr);
+    if (rc < 0) return fail(rc, "grid: %s", J.refused ? J.refused : umpa_hip_last_error());
+    return rc;
+}
+
+} // namespace
+
+UMPA_GRID_API const char* umpa_grid_last_error(void) { return g_err.c_str(); }
+
+UMPA_GRID_API int umpa_grid_match_region(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                         double* values, int nparam, double* uv, int* err,
+                                         const double* covermap, double cover_threshold,
+                                         double* dbg_d, double* dbg_a, int* dbg_ncalls, int flags, void* stream)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "grid: null model");
+    if (uv) return fail(UMPA_HIP_E_ARG, "grid search takes no start shifts (uv must be NULL)");
+    GridJob J;
+    return run(m, J, start0, step0, N0, start1, step1, N1, values, nparam, err, covermap, cover_threshold,
+               dbg_d, dbg_a, dbg_ncalls, flags, stream);
+}
+
+UMPA_GRID_API int umpa_grid_cost_volume(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                        double* cost, double* T, double* df, int flags, void* stream)
+{
+    if (!m || !cost) return fail(UMPA_HIP_E_ARG, "grid: null argument");
+    if (flags & ~UMPA_HIP_F_DEVICE_IO) return fail(UMPA_HIP_E_ARG, "grid: cost_volume takes UMPA_HIP_F_DEVICE_IO and no other flag");
+    GridJob J;
+    J.volume = true;
+    // the match entry point wants value and status arrays; this consumer's kernel touches neither, and with device I/O the
+    // entry point hands the pointers to the kernels as they are, nothing is copied, seeded or cleared (noted at that branch
+    // of umpa_hip_match_region): placeholders
+    double* const no_values = cost;
+    int* const no_err = (int*)cost;
+    if (flags & UMPA_HIP_F_DEVICE_IO) {
+        J.V.cost = cost; J.V.T = T; J.V.df = df;
+        J.want[2] = df != nullptr;
+        return run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                   UMPA_HIP_F_DEVICE_IO, stream);
+    }
+    // host arrays: device copies for the duration of the call, allocated by the consumer (the model's device is current
+    // there and stays this thread's current device afterwards), filled on that device's null stream
+    J.host = true; J.want[0] = true; J.want[1] = T != nullptr; J.want[2] = df != nullptr;
+    int rc = run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                 UMPA_HIP_F_DEVICE_IO, nullptr);
+    double* const host[3] = {cost, T, df};
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < 3 && rc >= 0 && e == hipSuccess; q++)
+        if (J.dev[q]) e = hipMemcpy(host[q], J.dev[q], J.count * sizeof(double), hipMemcpyDeviceToHost);
+    if (J.dev[0] || J.dev[1] || J.dev[2]) {                           // (none: refused before the consumer ran, nothing was enqueued)
+        if (rc < 0 || e != hipSuccess) (void)hipDeviceSynchronize();  // nothing of this call may still use the arrays freed here
+        for (int q = 0; q < 3; q++) if (J.dev[q]) (void)hipFree(J.dev[q]);
+    }
+    if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the cost volume: %s", hipGetErrorString(e));
+    return rc;
+}

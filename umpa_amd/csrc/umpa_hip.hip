@@ -21,6 +21,7 @@
 #include "umpa_walk.h"
 #include "umpa_direct.h"
 #include "umpa_tiled.h"
+#include "umpa_hipx.h"
 
 using namespace umpa;
 
@@ -186,8 +187,9 @@ struct umpa_hip_model {
 
 namespace {
 
-const char* const KERNEL_NAMES[] = {"match_direct", "coverage", "prep_maps", "corr_volume", "replay_walk", "match_staged", "corr_masked", "replay_cost", "blur_tiles", "corr_march"};
-enum { KN_DIRECT = 0, KN_COVER = 1, KN_PREP = 2, KN_CORR = 3, KN_REPLAY = 4, KN_STAGED = 5, KN_MASKED = 6, KN_REPLAY_COST = 7, KN_BLUR = 8, KN_MARCH = 9 };
+const char* const KERNEL_NAMES[] = {"match_direct", "coverage", "prep_maps", "corr_volume", "replay_walk", "match_staged", "corr_masked", "replay_cost", "blur_tiles", "corr_march", "table_consumer"};
+enum { KN_DIRECT = 0, KN_COVER = 1, KN_PREP = 2, KN_CORR = 3, KN_REPLAY = 4, KN_STAGED = 5, KN_MASKED = 6, KN_REPLAY_COST = 7, KN_BLUR = 8, KN_MARCH = 9,
+       KN_CONSUMER = 10 };   // (umpa_tiled.h brackets its launches by number: prep 2, corr 3, replay 4, march 9, a table consumer 10)
 
 hipEvent_t get_event(umpa_hip_model* m)
 {
@@ -617,6 +619,11 @@ int run_match(umpa_hip_model* m, const RegionArgs& A, int flags, hipStream_t s,
     // (every rectangle with a constant set of contributing frames can go there, run_stepping_cells)
     const bool cells = can_tile && !whole && m->Na <= 32;
     const bool split = cells || (can_tile && !whole && (size_t)(g.b0 - g.a0) * (g.b1 - g.a1) * 2 >= (size_t)A.N0 * A.N1);
+    // a table consumer (umpa_hipx.h) takes the plain tiled path's table of the whole region, nothing else
+    if (m->tiled.consumer && !(whole && !m->has_mask && !(flags & UMPA_HIP_F_FORCE_DIRECT)))
+        return fail(UMPA_HIP_E_UNSUPPORTED, "a table consumer is set (grid search / cost volume): the plain tiled path does not take "
+                                            "this model and region whole (masks, frames at different positions, steps or search "
+                                            "ranges past its limits, the kernel dark-field model, forced direct)");
     if ((flags & UMPA_HIP_F_FORCE_TILED) && !(whole || split))
         return fail(UMPA_HIP_E_UNSUPPORTED, "tiled path does not cover this model/region");
     if (whole && !(flags & UMPA_HIP_F_FORCE_DIRECT)) {
@@ -1026,6 +1033,9 @@ int umpa_hip_match_region(umpa_hip_model* m, int start0, int step0, int N0, int 
     A.dbg_d = dbg_d; A.dbg_a = dbg_a; A.dbg_n = dbg_ncalls;
 
     if (flags & UMPA_HIP_F_DEVICE_IO) {
+        // Nothing on this branch reads, seeds or clears the caller's arrays on the host side: they only reach the kernels.
+        // umpa_grid_cost_volume (umpa_grid.hip) relies on that: its consumer's kernel writes none of `values` / `err`, and
+        // it passes placeholders for them.  A memset or copy added here needs a real buffer there.
         if (int rc = adopt_staged(m, flags, (hipStream_t)stream)) return rc;
         if (m->rows_cb) {
             umpa_hip_rows_fn cb = m->rows_cb;
@@ -1315,6 +1325,14 @@ int umpa_hip_timing_fma(umpa_hip_model* m, int index, double* fma)
 }
 
 int umpa_hip_last_path(umpa_hip_model* m) { return m ? m->last_path : 0; }
+
+// (umpa_hipx.h: not part of the public header)
+int umpa_hipx_set_table_consumer(umpa_hip_model* m, umpa::TableConsumer fn, void* user)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "null model");
+    m->tiled.consumer = fn; m->tiled.consumer_user = fn ? user : nullptr;
+    return 0;
+}
 
 int umpa_hip_last_stats(umpa_hip_model* m, double* out4)
 {

@@ -496,7 +496,14 @@ replay_walk_kernel(ModelDev m, Maps M, ReplayArgs R, RegionArgs A, OdArgs od_in)
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// A consumer of the exhaustive shift table (umpa_hipx.h): where one is set on a model, tiled_match calls it for every row
+// chunk in place of the replay_walk launch -- the maps are filled, R describes the chunk's table and its output rows --
+// and it enqueues its own kernels on `s`.  Host code of another library built from these headers (libumpa_grid.so).
+typedef hipError_t (*TableConsumer)(void* user, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A,
+                                    hipStream_t s);
+
 struct TiledState {
+    TableConsumer consumer = nullptr;  void* consumer_user = nullptr;   // umpa_hipx_set_table_consumer
     double* maps = nullptr;   size_t maps_cap = 0;
     double* table = nullptr;  size_t table_cap = 0;
     bool table_limited = false;   // the budget's worth of table could not be allocated once: keep to the capacity we have
@@ -1282,7 +1289,8 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
     }
     if (MP.ok) N1p = MP.nstrips * MP.tw;                               // doubles per dense row and shift
     // on-demand passes of corr_march (od_run_chunk_lattice): UMPA_HIP_ONDEMAND=1 on, =0 off
-    const bool march_od = E.ondemand > 0 && MP.ok && MP.npass >= 3 && MP.npass <= 64 && !E.ablate_march;
+    // (a table consumer reads every plane: no on-demand stages while one is set)
+    const bool march_od = E.ondemand > 0 && MP.ok && MP.npass >= 3 && MP.npass <= 64 && !E.ablate_march && !st.consumer;
     long rows_chunk = 0;
     const int rc = tiled_table(st, E, (size_t)UJ * UJ * N1p, N0d, piece_rows, (size_t)N1p, rows_chunk);
     if (rc != 0) return rc;
@@ -1351,6 +1359,12 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
         };
         auto replay = [&](const OdArgs& od) {
             if (R.rows <= 0) return hipSuccess;
+            if (st.consumer) {                                        // the table goes to the consumer's kernels instead of the walk
+                tt.tic(10);                                           // KN_CONSUMER (umpa_hip.hip), "table_consumer"
+                const hipError_t ce = st.consumer(st.consumer_user, dev, M, R, A, s);
+                tt.toc();
+                return ce;
+            }
             dim3 blk(64, UMPA_REPLAY_ROWS), grd((A.N1 + 63) / 64, (R.rows + UMPA_REPLAY_ROWS - 1) / UMPA_REPLAY_ROWS);
             if (od.mode == 0 || od.mode == 2) {                       // (every pixel: blocks of 2^bw_log2 x 2^(6 - bw_log2) pixels per wave)
                 const int bw = 1 << R.bw_log2, bh = UMPA_REPLAY_ROWS * (64 >> R.bw_log2);
@@ -1418,7 +1432,7 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
                 return 0;
             }
         }
-        return tiled_chunk(st, CL, !MP.ok && od_enabled(E, ntiles, CL.npass, false) && !CA.ablate, (size_t)A.N0 * A.N1, s, tt, 3, corr, replay);
+        return tiled_chunk(st, CL, !MP.ok && !st.consumer && od_enabled(E, ntiles, CL.npass, false) && !CA.ablate, (size_t)A.N0 * A.N1, s, tt, 3, corr, replay);
     });
 }
 

@@ -320,7 +320,14 @@ class UMPAModelBase:
 
     # -- the match loop (model.pyx:334-497)
     def _match(self, step=None, input_values=None, dxdy=None, ROI=None,
-               num_threads=None, quiet=False):
+               num_threads=None, quiet=False, search='walk'):
+        if search not in ('walk', 'grid'):
+            raise ValueError("search must be 'walk' or 'grid', not %r" % (search,))
+        grid = search == 'grid'
+        if grid:
+            self._grid_check("search='grid'")
+            if dxdy is not None:
+                raise RuntimeError("search='grid' looks at every shift of the search box: start shifts (dxdy) mean nothing to it")
         if (ROI is not None) and (step is not None):
             print("Warning: 'ROI' and 'step' parameters are set simultaneously. "
                   "'step' parameter is ignored.")
@@ -391,7 +398,13 @@ class UMPAModelBase:
                 uv = np.zeros((N0, N1, 2), dtype=NPDOUBLE)
                 args[9] = vp(uv)
             args += [int(num_threads) if num_threads else max(1, self._lib.max_threads())]
-        self._lib.check(self._lib.match_region(*args), "match_region")
+        if grid:
+            try:
+                _lib.grid().check(_lib.grid().match_region(*args), "grid match_region")
+            except _lib.NativeError as e:
+                raise RuntimeError("search='grid': %s" % e) from None
+        else:
+            self._lib.check(self._lib.match_region(*args), "match_region")
 
         result['values'] = values
         result['_planar'] = planar
@@ -402,6 +415,58 @@ class UMPAModelBase:
                 result['debug_a'] = da
             result['debug_Ncalls'] = dn
         return result
+
+    # -- the exhaustive table's other consumers (include/umpa_grid.h)
+    def _grid_check(self, what):
+        """The grid kernels read the plain tiled path's table: what that path never takes whole is refused here by name,
+        the rest (steps, search ranges) by the library."""
+        why = None
+        if not self._lib.is_hip:
+            why = "it runs on the HIP library only"
+        elif self._kind == KIND_DFKERNEL:
+            why = "the kernel dark-field model has no shift table"
+        elif self._mask is not None:
+            why = "masked models are not supported (their table holds finished costs)"
+        elif not self._trivial_coverage():
+            why = "frames at different positions (pos_list) or of different shapes are not supported"
+        elif self._force & _lib.F_FORCE_DIRECT:
+            why = "the model is forced onto the direct kernel"
+        if why:
+            raise RuntimeError("%s (grid search / cost volume): %s" % (what, why))
+
+    def _cost_volume(self, ROI=None, step=None, with_fit=False):
+        self._grid_check("cost_volume")
+        if (ROI is not None) and (step is not None):
+            step = None
+        s0, s1 = self._convert_ROI_slice(ROI, step)
+        N0, N1 = self._counts(s0, s1)
+        self._check_range(s0, s1, N0, N1)
+        U = 2 * self._max_shift - 1
+        out = {'cost': np.empty((U, U, N0, N1), dtype=NPDOUBLE)}
+        if with_fit:
+            out['T'] = np.empty((U, U, N0, N1), dtype=NPDOUBLE)
+            if self._kind == KIND_DF:
+                out['df'] = np.empty((U, U, N0, N1), dtype=NPDOUBLE)
+        vp = lambda k: out[k].ctypes.data if k in out else None
+        try:
+            _lib.grid().check(_lib.grid().cost_volume(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1,
+                                                      vp('cost'), vp('T'), vp('df'), 0, None), "grid cost_volume")
+        except _lib.NativeError as e:
+            raise RuntimeError("cost_volume: %s" % e) from None
+        return out
+
+    _COST_VOLUME_DOC = """The cost of EVERY integer shift of the search box at every pixel of the region (extension; the
+        reference offers ``utils.get_cost``, a Python loop over ``cost()`` for one pixel): a dictionary with
+        ``cost[U, U, N0, N1]``, ``U = 2 max_shift - 1``, where ``cost[si + max_shift - 1, sj + max_shift - 1, xi, xj]``
+        is ``cost(i, j, si, sj)[0]`` of the region's pixel ``(xi, xj)`` (``si``: row shift, ``sj``: column shift) -- the
+        numbers ``match()`` compares, bit for bit.  ``with_fit=True`` adds ``T`` and, for the dark-field model, ``df`` in
+        the same layout.  ``ROI`` / ``step`` as for ``match()``; the model's own ROI is not changed.
+
+        Mind the size: an array holds ``U * U * N0 * N1`` doubles -- 2.7 GB for a whole 2048 x 2048 image at
+        ``max_shift=5`` -- so a ``ROI`` of the rows or the patch in question is the normal use.
+
+        Models the plain tiled path takes whole only (no masks, no ``pos_list``, steps and search ranges within its
+        limits); anything else raises ``RuntimeError``."""
 
     _force = 0
     _use_staged = False
@@ -587,9 +652,16 @@ class UMPAModelNoDF(UMPAModelBase):
                                        _lib._ptr(values, _lib._dp)), "cost")
         return (values[0], values[1])
 
-    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False):
-        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet)
+    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk'):
+        """``search='walk'`` (default): the reference's minimiser.  ``search='grid'`` (extension): the global minimum over
+        all ``(2 max_shift - 1)^2`` integer shifts, then the same sub-pixel step around it (``include/umpa_grid.h``);
+        plain models only (no masks, no ``pos_list``), no ``dxdy``."""
+        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet, search=search)
         return self._unpack(result, False)
+
+    def cost_volume(self, ROI=None, step=None, with_fit=False):
+        return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
+    cost_volume.__doc__ = UMPAModelBase._COST_VOLUME_DOC
 
 
 class UMPAModelDF(UMPAModelBase):
@@ -609,9 +681,16 @@ class UMPAModelDF(UMPAModelBase):
                                        _lib._ptr(values, _lib._dp)), "cost")
         return (values[0], values[1], values[2])
 
-    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False):
-        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet)
+    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk'):
+        """``search='walk'`` (default): the reference's minimiser.  ``search='grid'`` (extension): the global minimum over
+        all ``(2 max_shift - 1)^2`` integer shifts, then the same sub-pixel step around it (``include/umpa_grid.h``);
+        plain models only (no masks, no ``pos_list``), no ``dxdy``."""
+        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet, search=search)
         return self._unpack(result, True)
+
+    def cost_volume(self, ROI=None, step=None, with_fit=False):
+        return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
+    cost_volume.__doc__ = UMPAModelBase._COST_VOLUME_DOC
 
     @property
     def Im(self):
@@ -640,7 +719,11 @@ class UMPAModelDFKernel(UMPAModelBase):
                                        _lib._ptr(values, _lib._dp)), "cost")
         return (values[0], values[1])
 
-    def match(self, step=None, abc=None, dxdy=None, ROI=None, num_threads=None, quiet=False):
+    def match(self, step=None, abc=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk'):
+        if search not in ('walk', 'grid'):
+            raise ValueError("search must be 'walk' or 'grid', not %r" % (search,))
+        if search == 'grid':
+            self._grid_check("search='grid'")
         s0, s1 = self._convert_ROI_slice(ROI, step)
         self._set_ROI((s0, s1))
         N0, N1 = self._counts(s0, s1)
