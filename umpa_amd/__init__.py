@@ -6,10 +6,13 @@ Drop-in for the hot path of optimato/UMPA: ``match`` / ``match_unbiased`` and th
 (reference ``UMPA/__init__.py:8``, ``UMPA/speckle_matching.py``, ``UMPA/model.pyx``);
 the numerics run in ``libumpa_hip.so`` (C ABI: ``include/umpa_hip.h``).  ``align`` holds the three
 callers of ``UMPA/align.py`` that wrap the match (``UMPA_normal``, ``UMPA_nobias``, ``correct_bad_pixels``).
+``UnwarpMap`` (``umpa_amd.unwarp``) is the detector distortion correction of the reference's batch script.
 """
 from . import model
 from . import align
 from .model import UMPAModelNoDF, UMPAModelDF, UMPAModelDFKernel
 from .speckle_matching import match, match_unbiased
+from .unwarp import UnwarpMap
 
-__all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel"]
+__all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
+           "UnwarpMap"]

@@ -185,6 +185,52 @@ def grid():
     return _grid
 
 
+UNWARP_LIB_PATH = os.path.join(_HERE, "libumpa_unwarp.so")
+# every symbol include/umpa_unwarp.h declares
+UNWARP_SYMBOLS = ["map_create", "map_destroy", "frames", "attach", "last_error"]
+_unwarp = None
+
+
+class UnwarpNative:
+    """``libumpa_unwarp.so`` (``include/umpa_unwarp.h``): detector distortion correction, stand-alone and fused into
+    ``stage_sample`` of models of ``libumpa_hip.so``."""
+
+    def __init__(self, path):
+        if not os.path.exists(path):
+            raise NativeError(
+                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(there is no CPU fallback)" % path)
+        self.path = path
+        self.lib = C.CDLL(path)
+        self.map_create = self._f("map_create", C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int])
+        self.map_destroy = self._f("map_destroy", None, [C.c_void_p])
+        self.frames = self._f("frames", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
+        self.attach = self._f("attach", C.c_int, [C.c_void_p, C.c_void_p])
+        self.last_error = self._f("last_error", C.c_char_p, [])
+
+    def _f(self, name, restype, argtypes):
+        fn = getattr(self.lib, "umpa_unwarp_" + name)
+        fn.restype, fn.argtypes = restype, argtypes
+        return fn
+
+    def error(self):
+        return (self.last_error() or b"").decode()
+
+    def check(self, rc, what):
+        if rc is not None and rc < 0:
+            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
+        return rc
+
+
+def unwarp():
+    """The unwarp library, loaded at first use (after the product library it works on).  Raises if it is not built."""
+    global _unwarp
+    if _unwarp is None:
+        hip()
+        _unwarp = UnwarpNative(UNWARP_LIB_PATH)
+    return _unwarp
+
+
 ROWS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)       # umpa_hip_rows_fn
 
 

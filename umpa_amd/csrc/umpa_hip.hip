@@ -157,6 +157,8 @@ struct umpa_hip_model {
     struct PendingMatch { std::vector<hipEvent_t> events; hipEvent_t done; };
     std::vector<PendingMatch> pending;
     int out_set = 0;                               // device output set of the next host-array match
+    umpa_hipx_stage_filter stage_filter = nullptr; // umpa_hipx_set_stage_filter: called where stage_sample would launch flat_correct_kernel
+    void* stage_filter_user = nullptr;
     umpa_hip_rows_fn rows_cb = nullptr;            // umpa_hip_set_rows_callback: told after the kernels of a row piece are enqueued
     void* rows_user = nullptr;
     int rows_piece_rows = 0;
@@ -817,7 +819,7 @@ int umpa_hip_stage_sample(umpa_hip_model* m, const void* const* raw, int raw_dty
         size_t off = 0;
         for (int k = 0; k < m->Na; k++) { m->d_sam_back[k] = (double*)m->d_back_blob + off; off += (size_t)m->dims[2 * k] * m->dims[2 * k + 1]; }
     }
-    const bool convert = raw_dtype != 0 || dark || flat;
+    const bool convert = raw_dtype != 0 || dark || flat || m->stage_filter;
     if (convert && m->raw_cap < total * esz) {
         if (m->d_raw_blob) (void)hipFree(m->d_raw_blob);
         m->d_raw_blob = nullptr; m->raw_cap = 0;
@@ -841,7 +843,11 @@ int umpa_hip_stage_sample(umpa_hip_model* m, const void* const* raw, int raw_dty
             const double* dk = dark ? dark[k] : nullptr;
             const double* fl = flat ? flat[k] : nullptr;
             const unsigned grid = (unsigned)((n + 255) / 256);
-            if (raw_dtype == 0) hipLaunchKernelGGL((umpa::flat_correct_kernel<double>), dim3(grid), dim3(256), 0, us, (const double*)dr, dk, fl, out, n);
+            if (m->stage_filter) {
+                const int rc = m->stage_filter(m->stage_filter_user, k, dr, raw_dtype, dk, fl, out, m->dims[2 * k], m->dims[2 * k + 1], us);
+                if (rc < 0) return fail(rc, "the stage filter refused frame %d", k);
+            }
+            else if (raw_dtype == 0) hipLaunchKernelGGL((umpa::flat_correct_kernel<double>), dim3(grid), dim3(256), 0, us, (const double*)dr, dk, fl, out, n);
             else if (raw_dtype == 1) hipLaunchKernelGGL((umpa::flat_correct_kernel<float>), dim3(grid), dim3(256), 0, us, (const float*)dr, dk, fl, out, n);
             else hipLaunchKernelGGL((umpa::flat_correct_kernel<unsigned short>), dim3(grid), dim3(256), 0, us, (const unsigned short*)dr, dk, fl, out, n);
             HIP_TRY(hipGetLastError(), UMPA_HIP_E_LAUNCH);
@@ -917,6 +923,7 @@ void umpa_hip_destroy(umpa_hip_model* m)
     for (int q = 0; q < 2; q++) if (m->ev_read_done[q]) (void)hipEventDestroy(m->ev_read_done[q]);
     for (auto& pm : m->pending) { for (auto e : pm.events) (void)hipEventDestroy(e); if (pm.done) (void)hipEventDestroy(pm.done); }
     if (m->up_stream) { (void)hipStreamSynchronize(m->up_stream); (void)hipStreamDestroy(m->up_stream); }
+    if (m->stage_filter) (void)m->stage_filter(m->stage_filter_user, -1, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     if (m->copy_stream) (void)hipStreamDestroy(m->copy_stream);
     delete m;
@@ -1331,6 +1338,25 @@ int umpa_hipx_set_table_consumer(umpa_hip_model* m, umpa::TableConsumer fn, void
 {
     if (!m) return fail(UMPA_HIP_E_ARG, "null model");
     m->tiled.consumer = fn; m->tiled.consumer_user = fn ? user : nullptr;
+    return 0;
+}
+
+int umpa_hipx_set_stage_filter(umpa_hip_model* m, umpa_hipx_stage_filter fn, void* user, int H, int W, int device)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "null model");
+    if (fn) {
+        if (!m->owns_frames) return fail(UMPA_HIP_E_ARG, "the model borrows device frames: nothing is staged into them");
+        if (device != m->device) return fail(UMPA_HIP_E_ARG, "the filter's data is on device %d, the model on device %d", device, m->device);
+        for (int k = 0; k < m->Na; k++)
+            if (m->dims[2 * k] != H || m->dims[2 * k + 1] != W)
+                return fail(UMPA_HIP_E_UNSUPPORTED, "a map of %d x %d pixels, but frame %d of the model has %d x %d", H, W, k, m->dims[2 * k], m->dims[2 * k + 1]);
+    }
+    if (m->stage_filter) {
+        // what the old filter enqueued may still read its data: drain the upload stream before it is told to let go
+        if (m->up_stream) { (void)hipSetDevice(m->device); (void)hipStreamSynchronize(m->up_stream); }
+        (void)m->stage_filter(m->stage_filter_user, -1, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr);
+    }
+    m->stage_filter = fn; m->stage_filter_user = fn ? user : nullptr;
     return 0;
 }
 

@@ -1,12 +1,21 @@
 // umpa_hipx.h -- what libumpa_hip.so exports beside its public C ABI (include/umpa_hip.h), for libraries that are built from
-// these very headers by the same build and may therefore pass the internal structs: libumpa_grid.so (umpa_grid.hip).
+// these very headers by the same build and may therefore pass the internal structs: libumpa_grid.so (umpa_grid.hip) and
+// libumpa_unwarp.so (umpa_unwarp.hip).
 // Not installed, not versioned, not for other callers.
+//
+// UMPA_HIPX_STAGE_ONLY (defined by umpa_unwarp.hip before it includes this file): only the stage filter.  It passes no
+// internal struct, and a translation unit that includes umpa_tiled.h carries that header's kernels in its own code object
+// (and their compile time) whether it launches them or not.
 #pragma once
+#include <hip/hip_runtime.h>
 #include "../../include/umpa_hip.h"
+#ifndef UMPA_HIPX_STAGE_ONLY
 #include "umpa_tiled.h"
+#endif
 
 extern "C" {
 
+#ifndef UMPA_HIPX_STAGE_ONLY
 // Set (fn != NULL) or clear the model's table consumer (umpa::TableConsumer, umpa_tiled.h).  While one is set a match
 //   * must go down the plain tiled path whole (no masks, all frames at one position, steps and search range within the
 //     path's limits, not forced direct): anything else fails with UMPA_HIP_E_UNSUPPORTED before a kernel is launched;
@@ -15,5 +24,23 @@ extern "C" {
 //     launch replay_walk.
 // With no consumer set every launch is what it was.  The caller clears it again, also after a failed match.
 int umpa_hipx_set_table_consumer(umpa_hip_model* m, umpa::TableConsumer fn, void* user);
+#endif
+
+// A stage filter takes the place of flat_correct_kernel in umpa_hip_stage_sample: frame k of the raw stack (k >= 0) lies in
+// device memory as it came from the host (`raw_dtype`: 0 float64, 1 float32, 2 uint16); the filter enqueues, on
+// `upload_stream`, whatever writes the H x W float64 frame `out_k` of the model's back sample buffer from it (dark_k /
+// flat_k: the caller's device frames, or NULL) and returns 0 or a UMPA_HIP_E_* code.  k = -1 (every other argument 0) is
+// the release call: the model lets go of the filter -- it was replaced or cleared, or the model is being destroyed (after
+// its upload stream has drained) -- and never calls it again.
+typedef int (*umpa_hipx_stage_filter)(void* user, int k, const void* staged_raw, int raw_dtype, const double* dark_k,
+                                      const double* flat_k, double* out_k, int H, int W, hipStream_t upload_stream);
+
+// Set (fn != NULL) or clear the model's stage filter.  While one is set, umpa_hip_stage_sample always stages the raw bytes
+// on the device (a float64 stack without dark / flat too, which is otherwise copied straight into the sample buffer) and
+// calls `fn` per frame where it would launch flat_correct_kernel; events and the double buffer are what they were.
+// Setting is refused, and the filter in place stays, with UMPA_HIP_E_ARG for a model that borrows its frames and for
+// `device` other than the model's, with UMPA_HIP_E_UNSUPPORTED unless every frame of the model is H x W.  An earlier
+// filter gets its release call before the new one is installed.  With no filter set the call is what it was.
+int umpa_hipx_set_stage_filter(umpa_hip_model* m, umpa_hipx_stage_filter fn, void* user, int H, int W, int device);
 
 }

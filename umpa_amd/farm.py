@@ -21,7 +21,11 @@ projections from a queue, picks the nearest reference (``:133``), flat-corrects 
         ...
     farm.close()
 
-The loading / unwarping steps of the reference script are the caller's business (outside the matching path).
+The reference script's unwarp step (``umpa_multi.py:127-130``, its slowest) runs here too: with ``unwarp=`` an
+``umpa_amd.unwarp.UnwarpMap`` (``ProjectionFarm``: its ``(d0, d1, interp)``), every projection is resampled through the
+detector's distortion map by the kernel that carries it into the sample buffer, before ``(proj - dark) / flat``; references,
+flats and the dark frame are expected in unwarped geometry (``UnwarpMap.apply``).  Loading the raw frames stays the caller's
+business.
 """
 import multiprocessing as mp
 import os
@@ -49,7 +53,7 @@ class StreamingMatcher:
     """
 
     def __init__(self, refs, window_size, max_shift=4, df=True, device=0, flats=None, dark=None, ref_nums=None,
-                 model_cls=None, debug=False):
+                 model_cls=None, debug=False, unwarp=None):
         import torch
         from . import model as _model
         refs = np.asarray(refs, dtype=np.float64)
@@ -77,6 +81,8 @@ class StreamingMatcher:
         # the model owns device copies; the sample stack is replaced by every staged projection
         self.model = cls(np.zeros_like(self.refs[0]), self.refs[0], window_size=window_size, max_shift=max_shift, device=self.device)
         self.model.debug = debug
+        if unwarp is not None:             # an UnwarpMap on this device: every staged projection is unwarped on upload
+            self.model.set_unwarp(unwarp)
         self.out_alloc = None              # optional hook: (shape, dtype, zero) -> page-locked array (ProjectionFarm's result slots)
 
     # -- page-locked input buffers for producers that can write straight into them
@@ -200,8 +206,13 @@ def _farm_worker(device, cfg, tasks, results, in_name, out_name):
     import ctypes
     from . import _lib
     lib = _lib.hip()
+    uw = None
+    if cfg.get("unwarp") is not None:                              # (d0, d1, interp): each worker builds the map on its own device
+        from .unwarp import UnwarpMap
+        d0, d1, interp = cfg["unwarp"]
+        uw = UnwarpMap(d0, d1, interp=interp, device=device or 0)
     sm = StreamingMatcher(cfg["refs"], cfg["window_size"], cfg["max_shift"], df=cfg["df"], device=device or 0,
-                          flats=cfg["flats"], dark=cfg["dark"], ref_nums=cfg["ref_nums"])
+                          flats=cfg["flats"], dark=cfg["dark"], ref_nums=cfg["ref_nums"], unwarp=uw)
     slots_in = _Slots(None, cfg["depth_in"], cfg["in_bytes"], name=in_name)
     slots_out = _Slots(None, cfg["depth_out"], cfg["out_bytes"], name=out_name)
     # page-lock both rings once: uploads and downloads then run as DMA at link rate, straight from / into the
@@ -276,7 +287,7 @@ class ProjectionFailed(RuntimeError):
 
 class ProjectionFarm:
     def __init__(self, ref_stack, window_size, max_shift=4, df=True, devices=None, flats=None, dark=None, ref_nums=None,
-                 raw_dtype=np.float64, depth=2, worker=None, save_pattern=None):
+                 raw_dtype=np.float64, depth=2, worker=None, save_pattern=None, unwarp=None):
         """``devices``: HIP device indices, one worker process each (default: all visible devices).
         ``flats`` / ``dark`` / ``ref_nums``: the flat-field data of ``umpa_multi.py:133-145`` (optional).
         ``raw_dtype``: dtype of the projections as submitted (float64, float32 or uint16).
@@ -284,7 +295,9 @@ class ProjectionFarm:
         ``worker``: a picklable callable ``(device, cfg, tasks, results, in_name, out_name)`` to run in the worker processes
         instead of the GPU worker (same queue / slot protocol).  The package itself has no other worker; the CPU tests
         inject one of their own (tests/farm_cpu_worker.py) to exercise the farm's plumbing on machines without a GPU.
-        ``save_pattern``: e.g. ``"/data/out/umpa_%04d.npz"``: results are also written there (``umpa_multi.py:185``)."""
+        ``save_pattern``: e.g. ``"/data/out/umpa_%04d.npz"``: results are also written there (``umpa_multi.py:185``).
+        ``unwarp``: an ``UnwarpMap`` or ``(d0, d1, interp)``: every projection is unwarped on upload; the three items
+        travel in the worker configuration and each worker builds its map on its own device."""
         if devices is None:
             from . import _lib
             devices = list(range(max(1, _lib.hip().device_count())))
@@ -300,9 +313,16 @@ class ProjectionFarm:
         in_bytes = (self.K * self.H * self.W * self.raw_dtype.itemsize + 4095) & ~4095
         out_bytes = sum(((int(np.prod(s)) * np.dtype(d).itemsize + 63) & ~63) for _, s, d in _result_layout(self.N0, self.N1, df))
         out_bytes = (out_bytes + 4095) & ~4095
+        if unwarp is not None and not isinstance(unwarp, (tuple, list)):
+            unwarp = (unwarp.planes[0], unwarp.planes[1], unwarp.interp)
+        if unwarp is not None:
+            d0, d1, interp = unwarp
+            unwarp = (np.ascontiguousarray(d0, dtype=np.float32), np.ascontiguousarray(d1, dtype=np.float32), str(interp))
+            if unwarp[0].shape != (self.H, self.W) or unwarp[1].shape != (self.H, self.W):
+                raise ValueError("an unwarp map of %r for frames of %r" % (unwarp[0].shape, (self.H, self.W)))
         cfg = dict(refs=refs, window_size=int(window_size), max_shift=int(max_shift), df=self.df, flats=flats, dark=dark,
                    ref_nums=ref_nums, raw_dtype=self.raw_dtype.str, depth_in=depth, depth_out=depth, in_bytes=in_bytes,
-                   out_bytes=out_bytes)
+                   out_bytes=out_bytes, unwarp=unwarp)
         self._workers = []
         self._results = self._ctx.Queue()
         for d in devices:

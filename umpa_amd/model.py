@@ -522,6 +522,19 @@ class UMPAModelBase:
         self._staged_keep = (raw, dark, flat)                       # alive until the upload has been consumed
         self._use_staged = True
 
+    def set_unwarp(self, unwarp_map):
+        """Attach an ``umpa_amd.unwarp.UnwarpMap`` (or detach with None): while one is attached, ``stage_sample`` resamples
+        every raw frame through it on the way into the sample buffer, then applies ``(u - dark) / flat``
+        (``umpa_multi.py:130, :144``; ``include/umpa_unwarp.h``).  For models that own device copies of host frames, all of
+        the map's shape, on the map's device.  ``match()`` on the frames the model was built with is not affected."""
+        if not self._lib.is_hip:
+            raise RuntimeError('set_unwarp needs the HIP library.')
+        ulib = _lib.unwarp()
+        if unwarp_map is not None and unwarp_map._handle is None:
+            raise RuntimeError('the unwarp map was destroyed')
+        ulib.check(ulib.attach(self._handle, unwarp_map._handle if unwarp_map is not None else None), "unwarp attach")
+        self._unwarp = unwarp_map
+
     # -- properties (model.pyx:625-755)
     @property
     def extent(self):
