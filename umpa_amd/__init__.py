@@ -7,9 +7,12 @@ Drop-in for the hot path of optimato/UMPA: ``match`` / ``match_unbiased`` and th
 the numerics run in ``libumpa_hip.so`` (C ABI: ``include/umpa_hip.h``).  ``align`` holds the three
 callers of ``UMPA/align.py`` that wrap the match (``UMPA_normal``, ``UMPA_nobias``, ``correct_bad_pixels``).
 ``UnwarpMap`` (``umpa_amd.unwarp``) is the detector distortion correction of the reference's batch script.
+``umpa_amd.register`` holds the registration utilities of ``UMPA/align.py`` (``get_diff_pos``, ``get_new_sam_pos``,
+``shift_data`` ...) on ``libumpa_register.so``; ``align`` re-exports them.
 """
 from . import model
 from . import align
+from . import register
 from .model import UMPAModelNoDF, UMPAModelDF, UMPAModelDFKernel
 from .speckle_matching import match, match_unbiased
 from .unwarp import UnwarpMap

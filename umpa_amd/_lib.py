@@ -231,6 +231,50 @@ def unwarp():
     return _unwarp
 
 
+REGISTER_LIB_PATH = os.path.join(_HERE, "libumpa_register.so")
+# every symbol include/umpa_register.h declares
+REGISTER_SYMBOLS = ["sums", "last_error"]
+REGISTER_MAX_SHIFT = 32
+REGISTER_F_SHARED_A, REGISTER_F_SHARED_W = 256, 512
+_register = None
+
+
+class RegisterNative:
+    """``libumpa_register.so`` (``include/umpa_register.h``): the sums of the registration distance over a box of shifts."""
+
+    def __init__(self, path):
+        if not os.path.exists(path):
+            raise NativeError(
+                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(there is no CPU fallback)" % path)
+        self.path = path
+        self.lib = C.CDLL(path)
+        self.sums = self._f("sums", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p])
+        self.last_error = self._f("last_error", C.c_char_p, [])
+
+    def _f(self, name, restype, argtypes):
+        fn = getattr(self.lib, "umpa_register_" + name)
+        fn.restype, fn.argtypes = restype, argtypes
+        return fn
+
+    def error(self):
+        return (self.last_error() or b"").decode()
+
+    def check(self, rc, what):
+        if rc is not None and rc < 0:
+            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
+        return rc
+
+
+def register():
+    """The registration library, loaded at first use (after the product library it links).  Raises if it is not built."""
+    global _register
+    if _register is None:
+        hip()
+        _register = RegisterNative(REGISTER_LIB_PATH)
+    return _register
+
+
 ROWS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)       # umpa_hip_rows_fn
 
 

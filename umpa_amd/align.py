@@ -7,16 +7,25 @@ The callers next to the matching path that the reference keeps in ``UMPA/align.p
   ``_nobias``, a second match of the reference stack against itself whose ``dx``/``dy`` are
   subtracted) followed by the repair of ``dx`` and ``dy`` with the threshold ``shift``.
 
-Same signatures, defaults and result dictionaries as the reference.  The registration utilities of
-``align.py`` (``shift_best``, ``find_shift`` ...) are pre-processing and are not part of this package.
+Same signatures, defaults and result dictionaries as the reference.
+
+The registration utilities of ``align.py`` -- ``shift_dist``, ``shift_best``, ``get_diff_pos``, ``overlap``,
+``find_sam_shift``, ``get_new_sam_pos``, ``shift_data`` -- live in ``umpa_amd.register`` (``libumpa_register.so``: the
+distance over a bounded box of shifts instead of the reference's whole-frame FFTs) and are re-exported here, where users
+of the reference look for them; that module's docstring says what differs and what is left out (``find_shift``,
+``get_new_diff_pos``, the two-mask form of ``w``, ``numiter > 1``, plotting).
 """
 import ctypes
 
 import numpy as np
 
 from . import _lib, model
+from .register import (shift_sums, shift_dist, register, shift_best, get_diff_pos, overlap, find_sam_shift,  # noqa: F401
+                       get_new_sam_pos, solve_positions, shift_data)
 
-__all__ = ["correct_bad_pixels", "UMPA_normal", "UMPA_nobias"]
+__all__ = ["correct_bad_pixels", "UMPA_normal", "UMPA_nobias",
+           "shift_sums", "shift_dist", "register", "shift_best", "get_diff_pos", "overlap", "find_sam_shift",
+           "get_new_sam_pos", "solve_positions", "shift_data"]
 
 
 def correct_bad_pixels(img_in, th=None, iterations=1, dims=(-2, -1), p=0.5, device=None):
