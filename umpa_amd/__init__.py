@@ -9,6 +9,8 @@ callers of ``UMPA/align.py`` that wrap the match (``UMPA_normal``, ``UMPA_nobias
 ``UnwarpMap`` (``umpa_amd.unwarp``) is the detector distortion correction of the reference's batch script.
 ``umpa_amd.register`` holds the registration utilities of ``UMPA/align.py`` (``get_diff_pos``, ``get_new_sam_pos``,
 ``shift_data`` ...) on ``libumpa_register.so``; ``align`` re-exports them.
+``integrate`` / ``phase_from_match`` (``umpa_amd.integrate``) turn the differential maps ``dx``, ``dy`` into the phase by a
+weighted least-squares integration on ``libumpa_integrate.so``.
 """
 from . import model
 from . import align
@@ -16,6 +18,7 @@ from . import register
 from .model import UMPAModelNoDF, UMPAModelDF, UMPAModelDFKernel
 from .speckle_matching import match, match_unbiased
 from .unwarp import UnwarpMap
+from .integrate import integrate, vcycle, phase_from_match, Integration
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
-           "UnwarpMap"]
+           "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration"]

@@ -275,6 +275,53 @@ def register():
     return _register
 
 
+INTEGRATE_LIB_PATH = os.path.join(_HERE, "libumpa_integrate.so")
+# every symbol include/umpa_integrate.h declares
+INTEGRATE_SYMBOLS = ["solve", "vcycle", "last_error"]
+INTEGRATE_F_NO_TAIL, INTEGRATE_F_JACOBI, INTEGRATE_F_DEBUG = 256, 512, 1024
+INTEGRATE_CONVERGED, INTEGRATE_MAXITER, INTEGRATE_BREAKDOWN = 0, 1, 2
+INTEGRATE_CHECK_EVERY = 8
+_integrate = None
+
+
+class IntegrateNative:
+    """``libumpa_integrate.so`` (``include/umpa_integrate.h``): weighted least-squares phase integration."""
+
+    def __init__(self, path):
+        if not os.path.exists(path):
+            raise NativeError(
+                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(there is no CPU fallback)" % path)
+        self.path = path
+        self.lib = C.CDLL(path)
+        self.solve = self._f("solve", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_double, C.c_int, C.c_double] + [C.c_void_p] * 4
+                             + [C.c_int, C.c_int, C.c_void_p])
+        self.vcycle = self._f("vcycle", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p])
+        self.last_error = self._f("last_error", C.c_char_p, [])
+
+    def _f(self, name, restype, argtypes):
+        fn = getattr(self.lib, "umpa_integrate_" + name)
+        fn.restype, fn.argtypes = restype, argtypes
+        return fn
+
+    def error(self):
+        return (self.last_error() or b"").decode()
+
+    def check(self, rc, what):
+        if rc is not None and rc < 0:
+            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
+        return rc
+
+
+def integrate():
+    """The integration library, loaded at first use (after the product library it links).  Raises if it is not built."""
+    global _integrate
+    if _integrate is None:
+        hip()
+        _integrate = IntegrateNative(INTEGRATE_LIB_PATH)
+    return _integrate
+
+
 ROWS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)       # umpa_hip_rows_fn
 
 
