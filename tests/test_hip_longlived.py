@@ -1,0 +1,495 @@
+"""
+Long-lived models: what the libraries remember between calls, against a fresh model.
+
+A production run keeps one model alive for thousands of projections: frames are swapped under it (``update_frames``,
+``stage_sample``), the region, the window, the coordinate convention and the table budget change, matches run
+asynchronously, the grid search borrows the table.  Every one of these leans on state that survives a call -- the
+reference-side maps and the tile rectangle they were computed for (``TiledState::ref_maps_ok`` / ``ref_rect``), the grow-only
+map and table scratch, the two sample buffers and the descriptor lists that point into them, the two output sets, the
+unwarp attachment, the streaming matcher's current reference.  A stale piece of it faults nothing: it returns plausible
+maps computed from the wrong frames.
+
+A trajectory here is a list of steps applied to ONE model; beside it the harness keeps a plain record of what the model
+should now be.  After every match a fresh twin is built from that record, matched once with the same arguments under the
+same environment, and the two results must be equal bit for bit, ``last_path`` included.  No tolerance appears in this file.
+
+Each trajectory prints one line (steps compared, paths seen) for the record.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import REPO
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def hip_ns():
+    from umpa_amd import _lib, model
+    if _lib.hip().device_count() < 1:
+        pytest.fail("no HIP device: the GPU tests cannot run (there is no CPU fallback)")
+    return model
+
+
+def _copy(res):
+    return {k: np.array(v) for k, v in res.items() if isinstance(v, np.ndarray)}
+
+
+def _device_frames(a):
+    import torch
+    return list(torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0"))
+
+
+def _assert_same(got, want, need, what):
+    """bit for bit, on every array both results carry; the arrays in `need` must be among them"""
+    assert sorted(got) == sorted(want), (what, sorted(got), sorted(want))
+    assert set(need) <= set(got), (what, sorted(got))
+    for k in sorted(got):
+        assert got[k].shape == want[k].shape and got[k].dtype == want[k].dtype, (what, k)
+        if not np.array_equal(got[k], want[k], equal_nan=True):
+            bad = ~((got[k] == want[k]) | ((got[k] != got[k]) & (want[k] != want[k])))
+            first = tuple(int(x) for x in np.argwhere(bad)[0])
+            raise AssertionError("%s: %s differs from the fresh model's at %d of %d elements, first at %r: %r != %r" % (
+                what, k, int(bad.sum()), bad.size, first, got[k][first], want[k][first]))
+
+
+class LongLived:
+    """One model that stays alive, and the record a fresh twin is built from.
+
+    The record: model class, the sample stack -- a host array, or what was staged (raws, dark, flat: the twin stages the same
+    into its own sample buffer, so no host arithmetic stands in for the flat-correction kernel) --, the reference stack,
+    masks, positions, the window_size of the constructor (padding and extent are fixed there) and the Nw set since,
+    assign_coordinates, sub_pixel_mode, debug, the ROI, the forced path and the attached unwarp map."""
+
+    def __init__(self, hip_ns, cls, sam, ref, window_size, max_shift, mask=None, pos=None, force=0, label=""):
+        self.ns, self.label = hip_ns, label or cls
+        self.rec = dict(cls=cls, sam=("host", np.ascontiguousarray(sam)), ref=np.ascontiguousarray(ref), mask=mask, pos=pos,
+                        window_size=window_size, max_shift=max_shift, Nw=None, assign="sam", subpx=-1, debug=True, ROI=None,
+                        force=force, unwarp=None)
+        self.live = self._construct()
+        self.steps, self.paths = 0, []
+
+    # -- a model that has only ever been in the recorded state
+    def _construct(self):
+        r = self.rec
+        kw = dict(window_size=r["window_size"], max_shift=r["max_shift"])
+        if r["mask"] is not None:
+            kw["mask_list"] = r["mask"]
+        if r["pos"] is not None:
+            kw["pos_list"] = [np.array(p) for p in r["pos"]]
+        kind, payload = r["sam"]
+        m = getattr(self.ns, r["cls"])(payload if kind == "host" else np.zeros_like(r["ref"]), r["ref"], **kw)
+        m._force = r["force"]
+        if r["Nw"] is not None:
+            m.Nw = r["Nw"]
+        m.assign_coordinates = r["assign"]
+        m.sub_pixel_mode = r["subpx"]
+        m.debug = r["debug"]
+        if r["ROI"] is not None:
+            m.ROI = r["ROI"]
+        if kind == "staged":
+            raw, dark, flat = payload
+            if r["unwarp"] is not None:
+                m.set_unwarp(r["unwarp"])
+            m.stage_sample(list(raw), dark=dark, flat=flat)
+        return m
+
+    # -- mutations: the live model and the record together
+    def set(self, **attrs):
+        names = dict(Nw="Nw", assign="assign_coordinates", subpx="sub_pixel_mode", debug="debug", ROI="ROI")
+        for k, v in attrs.items():
+            setattr(self.live, names[k], v)
+            self.rec[k] = v
+
+    def update(self, sam=None, ref=None):
+        self.live.update_frames(sam_list=sam, ref_list=ref)
+        if sam is not None:
+            self.rec["sam"] = ("host", np.ascontiguousarray(sam))
+        if ref is not None:
+            self.rec["ref"] = np.ascontiguousarray(ref)
+
+    def stage(self, raw, dark=None, flat=None):
+        """float64 raws without dark / flat and without a map are copied as they are: the twin is BUILT with them (exact);
+        anything else goes through a kernel, and the twin stages the same raws into its own fresh model"""
+        self.live.stage_sample(list(raw), dark=dark, flat=flat)
+        plain = raw.dtype == np.float64 and dark is None and flat is None and self.rec["unwarp"] is None
+        self.rec["sam"] = ("host", np.ascontiguousarray(raw)) if plain else ("staged", (raw, dark, flat))
+
+    def unwarp(self, umap):
+        self.live.set_unwarp(umap)
+        self.rec["unwarp"] = umap
+
+    # -- matches: each against a twin that did only this call
+    def _path(self, m):
+        return m._lib.last_path(m._handle)
+
+    def _check(self, got, path, roi, call, what, expect_path=None, need=None):
+        """got, path, roi: the live model's maps, last_path and ROI after its call; `call(twin)` makes the same call"""
+        twin = self._construct()
+        want = _copy(call(twin))
+        self.steps += 1
+        self.paths.append(path)
+        tag = "%s, step %d (%s)" % (self.label, self.steps, what)
+        assert path == self._path(twin), "%s: last_path %d, the fresh model's %d" % (tag, path, self._path(twin))
+        if expect_path is not None:
+            assert path == expect_path, "%s: last_path %d, expected %d" % (tag, path, expect_path)
+        if need is None:
+            need = ("f", "T", "dx", "dy", "err") + (("df",) if self.rec["cls"] == "UMPAModelDF" else ())
+            need += ("debug_Ncalls",) if self.rec["debug"] else ()
+        _assert_same(got, want, need, tag)
+        assert roi == twin.ROI, "%s: ROI %r, the fresh model's %r" % (tag, roi, twin.ROI)
+        self.rec["ROI"] = twin.ROI
+        return got
+
+    def match(self, what="", expect_path=None, **kw):
+        got = _copy(self.live.match(quiet=True, **kw))
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: m.match(quiet=True, **kw), what or repr(kw), expect_path)
+
+    def match_async_pair(self, kw_a, kw_b):
+        """two asynchronous matches in flight (one per device output set), compared after their waits"""
+        ra = self.live.match_async(quiet=True, **kw_a)
+        pa, roi_a = self._path(self.live), self.live.ROI
+        rb = self.live.match_async(quiet=True, **kw_b)
+        pb, roi_b = self._path(self.live), self.live.ROI
+        self.live.wait()
+        self.live.wait()
+        ga, gb = _copy(ra), _copy(rb)
+        self._check(ga, pa, roi_a, lambda m: m.match(quiet=True, **kw_a), "async, first in flight %r" % (kw_a,))
+        self._check(gb, pb, roi_b, lambda m: m.match(quiet=True, **kw_b), "async, second in flight %r" % (kw_b,))
+
+    def cost_volume(self, **kw):
+        got = _copy(self.live.cost_volume(**kw))
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: m.cost_volume(**kw), "cost_volume %r" % (kw,),
+                           need=("cost",) + (("T", "df") if kw.get("with_fit") else ()))
+
+    def report(self):
+        print("\n[long-lived] %s: %d match steps compared, last_path values %s" % (self.label, self.steps, sorted(set(self.paths))))
+
+
+# ----------------------------------------------------------------------------- the tiles a region needs
+
+def _tile():
+    """PrepCfg<NW>::T as the source has it"""
+    tiled = open(os.path.join(REPO, "umpa_amd", "csrc", "umpa_tiled.h")).read()
+    corr = open(os.path.join(REPO, "umpa_amd", "csrc", "umpa_corr.h")).read()
+    assert re.search(r"struct PrepCfg \{\s*static constexpr int T = UMPA_TILE,", tiled), "PrepCfg<NW>::T is no longer UMPA_TILE"
+    return int(re.search(r"#define UMPA_TILE (\d+)", corr).group(1))
+
+
+def _prep_rect(H, W, NW, ms, pad, roi):
+    """prep_rect (umpa_tiled.h) restated: the tiles (tx0, tx1, ty0, ty1) of the maps a region reads"""
+    T = _tile()
+    ntx, nty = (W - 2 * NW + T - 1) // T, (H - 2 * NW + T - 1) // T
+    lo = lambda x: 0 if x - ms - NW < 0 else (x - ms - NW) // T
+    hi = lambda x, n: min(n, max(0, (x + ms - NW) // T + 1))
+    (a0, b0, s0), (a1, b1, s1) = roi
+    last0, last1 = a0 + s0 * ((b0 - a0 - 1) // s0), a1 + s1 * ((b1 - a1 - 1) // s1)
+    ty0 = min(lo(pad + a0), nty)
+    tx0 = min(lo(pad + a1), ntx)
+    return tx0, max(tx0, hi(pad + last1, ntx)), ty0, max(ty0, hi(pad + last0, nty))
+
+
+# 120 x 140 frames, window_size 4, max_shift 4: padding 8, 104 x 124 output pixels; T = 32 gives 5 x 4 tiles at Nw = 4 and 3.
+# The whole region reads tiles tx [0, 5) x ty [0, 4).
+#   ROI_IN   output rows 40..55, columns 40..59  -> tx [1, 3) x ty [1, 2) at Nw = 4, tx [1, 3) x ty [1, 3) at Nw = 3, 2:
+#            a strict subset of the tiles
+#   ROI_OUT  output rows 10..55, columns 40..99  -> tx [1, 4) x ty [0, 2) at Nw = 4, tx [1, 4) x ty [0, 3) at Nw = 3, 2:
+#            one tile row above and one tile column to the right of ROI_IN's rectangle (`covered` is false after ROI_IN)
+H1, W1, K1, WS1, MS1 = 120, 140, 6, 4, 4
+FULL = ((0, H1 - 2 * (WS1 + MS1), 1), (0, W1 - 2 * (WS1 + MS1), 1))
+ROI_IN = ((40, 56, 1), (40, 60, 1))
+ROI_OUT = ((10, 56, 1), (40, 100, 1))
+
+
+def test_the_two_rois_sit_on_the_tiles_as_described():
+    pad = WS1 + MS1
+    want = {4: ((1, 3, 1, 2), (1, 4, 0, 2)), 3: ((1, 3, 1, 3), (1, 4, 0, 3)), 2: ((1, 3, 1, 3), (1, 4, 0, 3))}
+    for NW in (4, 3, 2):
+        full = _prep_rect(H1, W1, NW, MS1, pad, FULL)
+        inner = _prep_rect(H1, W1, NW, MS1, pad, ROI_IN)
+        outer = _prep_rect(H1, W1, NW, MS1, pad, ROI_OUT)
+        assert full == (0, 5, 0, 4) and (inner, outer) == want[NW], (NW, full, inner, outer)
+        assert full[0] < inner[0] and inner[1] < full[1] and full[2] < inner[2] and inner[3] < full[3]     # strictly inside
+        assert outer[1] > inner[1] and outer[2] < inner[2]                                                  # past it on two sides
+
+
+_stacks = {}
+
+
+def _stack(seed, H=H1, W=W1, K=K1, ms=MS1, amplitude=1.5):
+    key = (seed, H, W, K, ms, amplitude)
+    if key not in _stacks:
+        from umpa_amd.synth import make_stack
+        sam, ref, _ = make_stack(H, W, K, ms, df=True, seed=seed, amplitude=amplitude)
+        sam.setflags(write=False)
+        ref.setflags(write=False)
+        _stacks[key] = (sam, ref)
+    return _stacks[key]
+
+
+# ----------------------------------------------------------------------------- 1. the plain tiled path
+
+@pytest.mark.parametrize("cls", ["UMPAModelDF", "UMPAModelNoDF"])
+def test_plain_tiled_path_over_regions_modes_and_windows(hip_ns, cls):
+    sam, ref = _stack(5)
+    t = LongLived(hip_ns, cls, sam, ref, WS1, MS1, label="1 plain " + cls)
+    t.match("whole region", expect_path=2, ROI=FULL)
+    t.match("the same again: the reference side is reused", expect_path=2, ROI=FULL)
+    t.match("interior ROI: a strict subset of the tiles", expect_path=2, ROI=ROI_IN)
+    t.match("ROI past that rectangle on two sides", expect_path=2, ROI=ROI_OUT)
+    t.match("whole region again", expect_path=2, ROI=FULL)
+    t.set(ROI=None)
+    t.match("step 2", step=2)
+    t.match("stepped ROI", ROI=((3, 100, 2), (5, 120, 3)))
+    t.set(assign="ref")
+    t.match("reference coordinates", ROI=FULL)
+    t.set(assign="sam")
+    t.match("sample coordinates again", ROI=FULL)
+    for subpx in (0, 1, -1):                                          # the modes of the goldens
+        t.set(subpx=subpx)
+        t.match("sub_pixel_mode %d" % subpx, ROI=ROI_OUT if subpx == 0 else FULL)
+    t.match("start shifts", ROI=FULL, dxdy=(1, -1))
+    for debug in ("ncalls", False, True):
+        t.set(debug=debug)
+        t.match("debug %r" % (debug,), ROI=ROI_IN if debug is False else FULL)
+    # a new window drops every map: the interior ROI then fills its own tiles only, and the larger one finds maps of the
+    # OLD window around them
+    for nw in (3, 2, 4, 3):
+        t.set(Nw=nw)
+        t.match("Nw %d, interior ROI" % nw, expect_path=2, ROI=ROI_IN)
+        t.match("Nw %d, ROI past it" % nw, expect_path=2, ROI=ROI_OUT)
+    t.match("whole region at the last window", expect_path=2, ROI=FULL)
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 2. frames swapped under the caches
+
+def _counts(sam, flat, dark):
+    return np.ascontiguousarray(np.clip(np.rint(sam * flat + dark), 0, 65535).astype(np.uint16))
+
+
+@pytest.mark.parametrize("cls", ["UMPAModelDF", "UMPAModelNoDF"])
+def test_frames_swapped_under_the_caches(hip_ns, cls):
+    samA, refA = _stack(5)
+    samB, refB = _stack(9, amplitude=2.0)
+    samC, refC = _stack(13)
+    rng = np.random.default_rng(3)
+    dark = 100.0 + rng.uniform(0, 2, size=samA.shape)
+    flat = 20000.0 * (1.0 + 0.05 * rng.standard_normal(samA.shape))
+    d_dark, d_flat = _device_frames(dark), _device_frames(flat)
+    t = LongLived(hip_ns, cls, samA, refA, WS1, MS1, label="2 swapped " + cls)
+    t.match("as built", expect_path=2, ROI=FULL)
+    t.update(sam=samB)
+    t.match("update_frames(sam)", ROI=FULL)
+    t.update(ref=refB)
+    t.match("update_frames(ref)", ROI=FULL)
+    t.update(sam=samC, ref=refC)
+    t.match("update_frames(both)", ROI=FULL)
+    t.stage(np.ascontiguousarray(samA))
+    t.match("stage_sample float64: the back blob is the front buffer now", ROI=FULL)
+    t.update(sam=samB)
+    t.match("update_frames(sam) into the back blob", ROI=FULL)
+    t.stage(_counts(samC, flat, dark), dark=d_dark, flat=d_flat)
+    t.match("stage_sample uint16 with dark and flat", ROI=FULL)
+    t.update(ref=refA)
+    t.match("update_frames(ref), then a ROI the previous rectangle covers", expect_path=2, ROI=ROI_IN)
+    t.match("... then a ROI past the tiles just computed", expect_path=2, ROI=ROI_OUT)
+    t.stage(np.ascontiguousarray(samA))
+    t.stage(np.ascontiguousarray(0.5 * samB))
+    t.match("two stage_sample calls, the second wins", ROI=FULL)
+    t.stage(_counts(samA, flat, dark), dark=d_dark, flat=d_flat)
+    t.match("stage_sample, then a ROI", ROI=ROI_IN)
+    t.match("... then the whole region", ROI=FULL)
+    t.update(sam=samC)
+    t.match("update_frames(sam) after an even number of swaps", ROI=FULL)
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 3. asynchronous matches
+
+def test_asynchronous_matches_in_both_output_sets(hip_ns):
+    sam, ref = _stack(5)
+    t = LongLived(hip_ns, "UMPAModelDF", sam, ref, WS1, MS1, label="3 async")
+    t.match_async_pair(dict(ROI=FULL), dict(ROI=ROI_IN))              # set 0 sized by the whole region, set 1 by the ROI
+    t.match_async_pair(dict(ROI=ROI_IN), dict(ROI=FULL))              # ... and the other way round
+    t.match_async_pair(dict(ROI=ROI_OUT), dict(ROI=((3, 100, 2), (5, 120, 3))))
+    t.match("synchronous afterwards", ROI=FULL)
+    t.match("and a ROI", ROI=ROI_IN)
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 4. masked models
+
+@pytest.mark.parametrize("kind", ["binary", "weights"])
+@pytest.mark.parametrize("cls", ["UMPAModelDF", "UMPAModelNoDF"])
+def test_masked_models_on_the_tiled_path(hip_ns, cls, kind):
+    """the 120 x 131, K = 3, Nw = 3, max_shift = 4 configuration of test_masked_models_against_the_oracle, path forced as there"""
+    from umpa_amd import _lib
+    H, W, K, Nw, ms = 120, 131, 3, 3, 4
+    samA, refA = _stack(77, H, W, K, ms, 2.0)
+    samB, refB = _stack(78, H, W, K, ms, 2.0)
+    rng = np.random.default_rng(5)
+    if kind == "binary":
+        mask = (rng.random(samA.shape) < 0.9).astype(np.float64)
+    else:
+        mask = rng.uniform(0.0, 1.0, size=samA.shape) * (rng.random(samA.shape) < 0.95)
+    full = ((0, H - 2 * (Nw + ms), 1), (0, W - 2 * (Nw + ms), 1))
+    t = LongLived(hip_ns, cls, samA, refA, Nw, ms, mask=mask, force=_lib.F_FORCE_TILED, label="4 masked %s %s" % (cls, kind))
+    t.match("as built", expect_path=2, ROI=full)
+    t.match("the same again: nothing is prepared", expect_path=2, ROI=full)
+    t.update(sam=samB)
+    t.match("update_frames(sam)", expect_path=2, ROI=full)
+    t.update(ref=refB)
+    t.match("update_frames(ref)", expect_path=2, ROI=full)
+    t.update(ref=refA)
+    t.match("update_frames(ref), small ROI", expect_path=2, ROI=((40, 56, 1), (40, 60, 1)))
+    t.match("a larger ROI after the smaller one", expect_path=2, ROI=((10, 56, 1), (40, 100, 1)))
+    t.set(Nw=2)
+    t.match("Nw 2, small ROI", expect_path=2, ROI=((40, 56, 1), (40, 60, 1)))
+    t.match("Nw 2, whole region", expect_path=2, ROI=full)
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 5. sample stepping
+
+def test_sample_stepping_with_cached_subset_descriptors(hip_ns):
+    """Three frames at (0, 0), (2, 1), (1, 3).  Frame k contributes to the output rows pi .. pi + H - 2 pad and columns
+    pj .. pj + W - 2 pad (run_stepping_cells), so the rectangles of the region with a constant set of contributing frames
+    are the centre (every frame: rows 2 .. H - 2 pad, columns 3 .. W - 2 pad) and strips one or two pixels wide around
+    it; only those of 1024 pixels (UMPA_STEP_CELL_MIN) and more run on the tiled path, with a cached descriptor list of
+    their subset.  The column strips beside the centre are H - 11 rows tall: column 0 (frame 0), columns 1..2 (frames 0, 1),
+    column W - 9 (frames 1, 2) and column W - 8 (frame 2).  One-column strips of 1024 pixels take frames 1035 rows tall --
+    taller than the other trajectories', and narrow instead (1040 x 24: fewer pixels than 160 x 180)."""
+    H, W, K, Nw, ms = 1040, 24, 3, 2, 3
+    pos = ((0, 0), (2, 1), (1, 3))
+    pad = Nw + ms
+    assert H - 2 * pad - 1 >= 1024                                    # rows 2 .. H - 2 pad of a one-column strip
+    samA, refA = _stack(21, H, W, K, ms, 1.0)
+    samB, refB = _stack(22, H, W, K, ms, 1.0)
+    t = LongLived(hip_ns, "UMPAModelDF", samA, refA, Nw, ms, pos=pos, label="5 stepping")
+    N0, N1 = t.live.extent
+    assert (N0, N1) == (H + 2 - 2 * pad, W + 3 - 2 * pad)
+    full = ((0, N0, 1), (0, N1, 1))
+    inside = ((10, 1000, 1), (4, 14, 1))                              # within rows 2 .. H - 2 pad, columns 3 .. W - 2 pad: every frame
+    # the first match, with the library's timers: the centre and the four strips each launch the table kernel
+    import ctypes
+    lib, h = t.live._lib, t.live._handle
+    lib.timing_enable(h, 1)
+    t.match("whole region", expect_path=4, ROI=full)
+    seen = {}
+    for q in range(lib.timing_collect(h)):
+        nm, tot, cnt = ctypes.c_char_p(), ctypes.c_double(), ctypes.c_int()
+        lib.timing_read(h, q, ctypes.byref(nm), ctypes.byref(tot), ctypes.byref(cnt))
+        seen[nm.value.decode()] = cnt.value
+    lib.timing_enable(h, 0)
+    assert seen.get("corr_volume", 0) == 5, sorted(seen.items())
+    t.match("the same again: cached descriptor lists", expect_path=4, ROI=full)
+    t.stage(np.ascontiguousarray(samB))
+    t.match("stage_sample: the cached lists hold the old sample pointers", expect_path=4, ROI=full)
+    t.update(ref=refB)
+    t.match("update_frames(ref)", expect_path=4, ROI=full)
+    t.match("a ROI every frame covers", expect_path=2, ROI=inside)
+    t.match("the whole region: subset planes over the all-frames planes", expect_path=4, ROI=full)
+    t.match("that ROI again", expect_path=2, ROI=inside)
+    t.stage(np.ascontiguousarray(samA))
+    t.match("stage_sample back into the first buffer", expect_path=4, ROI=full)
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 6. the table and its consumer
+
+def test_table_budget_and_grid_consumer_on_one_model(hip_ns, monkeypatch):
+    """the 400 x 300 x 4 stack of test_stepped_and_chunked_tiled_path_matches_direct: 49 planes of 288 doubles per dense row,
+    so 16 MB hold 128 rows and the 386 rows fall into four chunks -- under a table the default budget allocated whole"""
+    from umpa_amd.synth import make_stack
+    sam, ref, _ = make_stack(400, 300, 4, 4, df=True, seed=77, amplitude=1.5, order=1)
+    monkeypatch.delenv("UMPA_HIP_TABLE_MB", raising=False)
+    t = LongLived(hip_ns, "UMPAModelDF", sam, ref, 3, 4, label="6 table")
+    t.set(debug="ncalls")
+    full = ((0, 386, 1), (0, 286, 1))
+    roi = ((17, 300, 2), (5, 280, 3))
+    t.match("default budget: one chunk", expect_path=2, ROI=full)
+    t.match("grid search, one chunk", expect_path=2, ROI=full, search="grid")
+    monkeypatch.setenv("UMPA_HIP_TABLE_MB", "16")
+    t.match("16 MB: four chunks under the larger table", expect_path=2, ROI=full)
+    t.cost_volume(ROI=((100, 140, 1), (50, 90, 1)), with_fit=True)
+    t.match("stepped ROI, chunked", expect_path=2, ROI=roi)
+    t.match("grid search, four chunks", expect_path=2, ROI=full, search="grid")
+    t.match("the walk after the consumer", expect_path=2, ROI=full)
+    monkeypatch.delenv("UMPA_HIP_TABLE_MB")
+    t.cost_volume(ROI=((0, 386, 4), (0, 286, 4)))
+    t.match("default budget again", expect_path=2, ROI=full)
+    t.match("grid search on a ROI", expect_path=2, ROI=roi, search="grid")
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 7. the unwarp attachment over time
+
+def test_unwarp_attachment_over_time(hip_ns):
+    import test_hip_unwarp as TU
+    import unwarp_expect as UE
+    from umpa_amd import UnwarpMap
+    refs, flats, dark, raws = TU.series()
+    map_a = UnwarpMap(*UE.radial_map(TU.MH, TU.MW), interp="cubic")
+    map_b = UnwarpMap(*UE.radial_map(TU.MH, TU.MW, amplitude=2.0, seed=11), interp="linear")
+    d_dark, d_flat = _device_frames(dark), _device_frames(flats[0])
+    t = LongLived(hip_ns, "UMPAModelDF", np.zeros_like(refs[0]), refs[0], TU.Nw, TU.MS, label="7 unwarp")
+    t.unwarp(map_a)
+    t.stage(raws[0], dark=d_dark, flat=d_flat)
+    a0 = t.match("map A")
+    t.unwarp(map_b)
+    t.stage(raws[0], dark=d_dark, flat=d_flat)
+    b0 = t.match("map B attached over A")
+    t.unwarp(None)
+    t.stage(raws[0], dark=d_dark, flat=d_flat)
+    n0 = t.match("detached")
+    t.unwarp(map_a)
+    t.stage(raws[2], dark=d_dark, flat=d_flat)
+    t.match("map A again, another projection")
+    t.stage(raws[0], dark=d_dark, flat=d_flat)
+    a1 = t.match("map A, the first projection again")
+    # the three states are three different answers, so the comparisons above could tell them apart
+    assert not np.array_equal(a0["dx"], b0["dx"]) and not np.array_equal(a0["dx"], n0["dx"]) and not np.array_equal(b0["dx"], n0["dx"])
+    assert np.array_equal(a0["dx"], a1["dx"])
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 8. StreamingMatcher used more than once
+
+@pytest.mark.parametrize("unwarp", [False, True], ids=["plain", "unwarp"])
+def test_streaming_matcher_used_more_than_once(hip_ns, unwarp):
+    """Projection numbers 0, 1, 0.25, 0.75 against references acquired at 0 and 1: the nearest reference alternates, as the
+    flats of the series do.  The second run is left at its first yield -- the hand-out before the first reference switch,
+    with projection 1 staged and not yet adopted."""
+    import test_hip_unwarp as TU
+    import unwarp_expect as UE
+    from umpa_amd import UnwarpMap
+    from umpa_amd.farm import StreamingMatcher
+    refs, flats, dark, raws = TU.series()
+    ids = [0.0, 1.0, 0.25, 0.75]
+    umap = UnwarpMap(*UE.radial_map(TU.MH, TU.MW), interp="cubic") if unwarp else None
+
+    def matcher():
+        return StreamingMatcher(refs, TU.Nw, TU.MS, df=True, device=0, flats=flats, dark=dark, ref_nums=[0, 1], unwarp=umap)
+
+    def items():
+        return ((ids[p], raws[p]) for p in range(4))
+
+    sm = matcher()
+    first = [(pid, _copy(res)) for pid, res in sm.run(items())]
+    gen = sm.run(items())
+    pid, _res = next(gen)
+    assert pid == ids[0] and sm.model._use_staged                     # the next projection is staged, its match not enqueued
+    gen.close()
+    third = [(pid, _copy(res)) for pid, res in sm.run(items())]
+    want = [(pid, _copy(res)) for pid, res in matcher().run(items())]
+    assert [p for p, _ in first] == [p for p, _ in third] == [p for p, _ in want] == ids
+    for run, what in ((first, "first run"), (third, "run after an abandoned one")):
+        for (pid, got), (_, exp) in zip(run, want):
+            assert exp["err"].mean() > 0.5
+            _assert_same(got, exp, ("f", "T", "dx", "dy", "df", "err"), "8 streaming %s, projection %r" % (what, pid))
+    assert not np.array_equal(want[0][1]["dx"], want[2][1]["dx"])     # (the projections differ: a mix-up would show)
+    print("\n[long-lived] 8 streaming %s: %d projections compared" % ("unwarp" if unwarp else "plain", 2 * len(want)))

@@ -432,3 +432,27 @@ def test_watchdog_ends_a_wedged_rank():
     assert "quick phase done" in out.stdout and "not reached" not in out.stdout
     assert "rank 5" in out.stderr and "halo exchange" in out.stderr
     assert time.time() - t0 < 20
+
+
+def test_watchdog_phases_nest():
+    """Leaving an inner phase leaves the outer one armed with the deadline it was entered with (one slot used to serve both:
+    the inner exit disarmed the outer phase).  The state is inspected; nothing fires."""
+    from umpa_amd.sharding import Watchdog
+    wd = Watchdog(rank=0)
+    try:
+        assert wd._armed is None
+        with wd.phase("step", 3600.0):
+            outer = wd._armed
+            assert outer[0] == "step" and outer[2] == 3600.0
+            with wd.phase("barrier", 1800.0):
+                inner = wd._armed
+                assert inner[0] == "barrier" and inner[2] == 1800.0 and inner[1] < outer[1]
+            assert wd._armed == outer                                # the same name, deadline and length as on entry
+            with pytest.raises(KeyError):                            # an inner phase that raises restores the outer one too
+                with wd.phase("barrier", 1800.0):
+                    raise KeyError("x")
+            assert wd._armed == outer
+        assert wd._armed is None
+        assert wd.fired is None
+    finally:
+        wd.close()

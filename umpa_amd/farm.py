@@ -31,6 +31,7 @@ import multiprocessing as mp
 import os
 import queue as _queue
 import time
+from collections import deque
 
 import numpy as np
 
@@ -107,7 +108,6 @@ class StreamingMatcher:
         """``items`` yields ``(proj_num, raw_stack)``; yields ``(proj_num, result)`` in the same order.  Two matches are
         in flight: while the maps of projection p travel to the host, projection p+1 is being matched (into the library's
         other device output set) and projection p+2 is on its way to the GPU."""
-        from collections import deque
         match_kw.setdefault("quiet", True)
         it = iter(items)
         pending = deque()
@@ -334,6 +334,7 @@ class ProjectionFarm:
             w["proc"].start()
             self._workers.append(w)
         self._by_seq = {}                                           # in flight: internal sequence number -> (worker, caller's id)
+        self._held = deque()                                        # messages taken off the queue ahead of _collect
         self._seq = 0
         self._alive = len(self._workers)
 
@@ -373,7 +374,10 @@ class ProjectionFarm:
         deadline = time.time() + timeout
         while True:
             try:
-                kind, pid, q_in, q_out, err = self._results.get(timeout=1.0)
+                if self._held:                                      # "done" messages _raise_if_dead came across
+                    kind, pid, q_in, q_out, err = self._held.popleft()
+                else:
+                    kind, pid, q_in, q_out, err = self._results.get(timeout=1.0)
             except _queue.Empty:
                 dead = [w for w in self._workers if w["inflight"] and not w["proc"].is_alive()]
                 if dead:
@@ -410,67 +414,98 @@ class ProjectionFarm:
             return pid, res, release
 
     def _raise_if_dead(self, timeout):
-        """Called when no input slot can be had and nothing is in flight: drain the workers' messages (raising on 'error'
-        and once every worker has exited); blocks for at most a second."""
+        """Called when no input slot can be had and nothing of this map() is in flight: look at the workers' next message
+        (raising on 'error' and once every worker has exited); blocks for at most a second.  A "done" message seen here
+        belongs to a projection submitted outside map(): it is kept for the ``_collect`` that asks for it, slots and all."""
         try:
-            kind, _a, _b, _c, err = self._results.get(timeout=1.0)
+            msg = self._results.get(timeout=1.0)
         except _queue.Empty:
             if not any(w["proc"].is_alive() for w in self._workers):
                 raise RuntimeError("all farm workers have exited")
             return
+        kind, err = msg[0], msg[4]
         if kind == "error":
             raise RuntimeError("farm worker failed: %s" % err)
         if kind == "exit":
             self._alive -= 1
             if self._alive <= 0:
                 raise RuntimeError("all farm workers have exited")
+            return
+        self._held.append(msg)
+
+    def _drain(self, inflight, timeout):
+        """Collect and release the ``inflight`` projections a map() leaves behind; their results and their failures are
+        dropped.  Bounded by ``timeout`` seconds in all."""
+        deadline = time.time() + timeout
+        while inflight:
+            try:
+                _pid, _res, release = self._collect(max(0.0, deadline - time.time()))
+            except ProjectionFailed:
+                inflight -= 1
+                continue
+            release()
+            inflight -= 1
 
     def map(self, projections, timeout=600.0, **match_kw):
         """Yield ``(id, result dict)`` as projections complete (not in submission order).  Convenience form: every
         projection is copied into an input slot and every result out of its slot; producers that can write into
-        ``input_buffer()`` arrays and consumers that can work on the slot views (``_collect``) avoid both copies."""
+        ``input_buffer()`` arrays and consumers that can work on the slot views (``_collect``) avoid both copies.
+
+        However the call ends -- exhaustion, a ``break`` or ``close()`` of the generator, an exception from the consumer or
+        from ``projections`` -- what it still has in flight is collected and released before it returns: the next ``map()``
+        on this farm starts with every slot free and sees its own results only."""
         it = iter(projections)
         exhausted = False
         inflight = 0
         failed = None
-        while not exhausted or inflight:
-            while not exhausted:
-                got = self.input_buffer()
-                if got is None:
-                    break
-                try:
-                    pid, sam = next(it)
-                except StopIteration:
-                    exhausted = True
-                    w, q = got[0]
-                    w["free_in"].append(q)
-                    break
-                handle, arr = got
-                arr[...] = sam
-                self.submit(pid, handle, **match_kw)
-                inflight += 1
-            if not inflight and not exhausted:
-                # no free slot although nothing is in flight: no worker is alive (each posts 'error' / 'exit' when it
-                # dies, e.g. in its constructor): surface that instead of spinning
-                self._raise_if_dead(timeout)
-                continue
-            if inflight:
-                try:
-                    pid, res, release = self._collect(timeout)
-                except ProjectionFailed as e:
-                    # this projection is lost, the ones still in flight are not: nothing new is submitted, what is in
-                    # flight is collected (and handed out), then the first failure is raised -- a later map() on this farm
-                    # finds no stale results in the queue (ADVICE round 3)
-                    failed = failed or e
-                    inflight -= 1
-                    exhausted = True
+        starved = None
+        try:
+            while not exhausted or inflight:
+                while not exhausted:
+                    got = self.input_buffer()
+                    if got is None:
+                        break
+                    handle, arr = got
+                    try:
+                        pid, sam = next(it)
+                        arr[...] = sam
+                    except BaseException as e:                      # the slot goes back whatever the iterator did
+                        handle[0]["free_in"].append(handle[1])
+                        if not isinstance(e, StopIteration):
+                            raise
+                        exhausted = True
+                        break
+                    self.submit(pid, handle, **match_kw)
+                    inflight += 1
+                if not inflight and not exhausted:
+                    # no free slot although nothing of this call is in flight: no worker is alive (each posts 'error' /
+                    # 'exit' when it dies, e.g. in its constructor), or projections submitted outside map() hold every
+                    # slot: surface either instead of spinning
+                    starved = starved or time.time()
+                    if time.time() - starved > timeout:
+                        raise RuntimeError("no free farm slot for %.0f s with nothing of this map() in flight" % timeout)
+                    self._raise_if_dead(timeout)
                     continue
-                out = {k: np.array(v) for k, v in res.items()}
-                if self.save_pattern:
-                    np.savez(self.save_pattern % pid, **out)
-                release()
-                inflight -= 1
-                yield pid, out
+                starved = None
+                if inflight:
+                    try:
+                        pid, res, release = self._collect(timeout)
+                    except ProjectionFailed as e:
+                        # this projection is lost, the ones still in flight are not: nothing new is submitted, what is in
+                        # flight is collected (and handed out), then the first failure is raised -- a later map() on this
+                        # farm finds no stale results in the queue (ADVICE round 3)
+                        failed = failed or e
+                        inflight -= 1
+                        exhausted = True
+                        continue
+                    out = {k: np.array(v) for k, v in res.items()}
+                    if self.save_pattern:
+                        np.savez(self.save_pattern % pid, **out)
+                    release()
+                    inflight -= 1
+                    yield pid, out
+        finally:
+            self._drain(inflight, timeout)
         if failed is not None:
             raise failed
 

@@ -225,7 +225,7 @@ class Watchdog:
         self.rank, self.exit_code = int(rank), int(exit_code)
         self._stream = stream
         self._lock = threading.Lock()
-        self._armed = None                                          # (name, deadline, seconds)
+        self._stack = []                                            # (name, deadline, seconds), outermost phase first
         self._stop = False
         self.fired = None
         self._thread = threading.Thread(target=self._run, name="umpa-watchdog", daemon=True)
@@ -236,9 +236,10 @@ class Watchdog:
         import time
         while not self._stop:
             time.sleep(0.2)
-            with self._lock:
-                armed = self._armed
-            if armed and time.monotonic() > armed[1]:
+            now = time.monotonic()
+            with self._lock:                                        # an outer phase's deadline holds while an inner one runs
+                armed = next((a for a in self._stack if now > a[1]), None)
+            if armed:
                 msg = "[umpa watchdog] rank %d: phase %r still running after %.0f s -- ending this process (exit code %d)\n" % (
                     self.rank, armed[0], armed[2], self.exit_code)
                 (self._stream or sys.stderr).write(msg)
@@ -251,19 +252,27 @@ class Watchdog:
         import os
         os._exit(code)
 
+    @property
+    def _armed(self):
+        """The innermost phase that is running, or None."""
+        with self._lock:
+            return self._stack[-1] if self._stack else None
+
     def phase(self, name, seconds):
+        """Phases nest: leaving an inner phase leaves the outer one armed with the deadline it was entered with."""
         import contextlib
         import time
 
         @contextlib.contextmanager
         def cm():
+            entry = (name, time.monotonic() + float(seconds), float(seconds))
             with self._lock:
-                self._armed = (name, time.monotonic() + float(seconds), float(seconds))
+                self._stack.append(entry)
             try:
                 yield
             finally:
                 with self._lock:
-                    self._armed = None
+                    self._stack.remove(entry)
         return cm()
 
     def close(self):
