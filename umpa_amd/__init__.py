@@ -11,6 +11,8 @@ callers of ``UMPA/align.py`` that wrap the match (``UMPA_normal``, ``UMPA_nobias
 ``shift_data`` ...) on ``libumpa_register.so``; ``align`` re-exports them.
 ``integrate`` / ``phase_from_match`` (``umpa_amd.integrate``) turn the differential maps ``dx``, ``dy`` into the phase by a
 weighted least-squares integration on ``libumpa_integrate.so``.
+``KernelSearch`` (``umpa_amd.ddf``) finds the blur kernel ``(a, b, c)`` of the kernel dark-field model among candidates, per
+pixel, on ``libumpa_ddf.so``: the directional dark-field signal.
 """
 from . import model
 from . import align
@@ -19,6 +21,9 @@ from .model import UMPAModelNoDF, UMPAModelDF, UMPAModelDFKernel
 from .speckle_matching import match, match_unbiased
 from .unwarp import UnwarpMap
 from .integrate import integrate, vcycle, phase_from_match, Integration
+from . import ddf
+from .ddf import (KernelSearch, gaussian_kernel, kernel_from_sigma, sigma_from_kernel, candidate_grid, blur_frames)
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
-           "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration"]
+           "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration",
+           "ddf", "KernelSearch", "gaussian_kernel", "kernel_from_sigma", "sigma_from_kernel", "candidate_grid", "blur_frames"]

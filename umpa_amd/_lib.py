@@ -322,6 +322,52 @@ def integrate():
     return _integrate
 
 
+DDF_LIB_PATH = os.path.join(_HERE, "libumpa_ddf.so")
+# every symbol include/umpa_ddf.h declares
+DDF_SYMBOLS = ["kernel", "blur", "fold", "last_error"]
+DDF_TAPS, DDF_HALF, DDF_MAX_FRAMES = 17, 8, 32
+_ddf = None
+
+
+class DdfNative:
+    """``libumpa_ddf.so`` (``include/umpa_ddf.h``): the whole-image blur and the candidate fold of the directional
+    dark-field search."""
+
+    def __init__(self, path):
+        if not os.path.exists(path):
+            raise NativeError(
+                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(there is no CPU fallback)" % path)
+        self.path = path
+        self.lib = C.CDLL(path)
+        self.kernel = self._f("kernel", C.c_int, [C.c_double] * 3 + [C.c_void_p])
+        self.blur = self._f("blur", C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p])
+        self.fold = self._f("fold", C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_void_p])
+        self.last_error = self._f("last_error", C.c_char_p, [])
+
+    def _f(self, name, restype, argtypes):
+        fn = getattr(self.lib, "umpa_ddf_" + name)
+        fn.restype, fn.argtypes = restype, argtypes
+        return fn
+
+    def error(self):
+        return (self.last_error() or b"").decode()
+
+    def check(self, rc, what):
+        if rc is not None and rc < 0:
+            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
+        return rc
+
+
+def ddf():
+    """The dark-field search library, loaded at first use (after the product library it links).  Raises if it is not built."""
+    global _ddf
+    if _ddf is None:
+        hip()
+        _ddf = DdfNative(DDF_LIB_PATH)
+    return _ddf
+
+
 ROWS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)       # umpa_hip_rows_fn
 
 
