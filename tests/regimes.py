@@ -148,6 +148,28 @@ CONFIGS = {
 }
 
 
+# Further sample-stepping configurations for tests/test_hip_borrowed.py: the branch with the most host logic that only
+# borrowed device frames reach (pair_slack, umpa_hip.hip).  They stand beside CONFIGS, not in it: every entry of CONFIGS is
+# swept over all regimes by test_regimes_cpu.py / test_hip_regimes.py against recorded files (tests/golden/regime_observed.json,
+# bad_pixel_agreement.npz), and the stacks' seeds go with the sorted names of CONFIGS.  `config(name)` finds both.
+#   stepping_mask_DF, stepping_NoDF: the geometry of stepping_DF -- the centre rectangle (every frame, 102 x 119 pixels) is the
+#     one tiled rectangle, every strip around it is below UMPA_STEP_CELL_MIN = 1024 pixels;
+#   stepping_s2: a stepped ROI whose strips are tiled rectangles too, with descriptor lists of frame subsets: rows 17..68 x
+#     columns 0..19 (frames 0, 2: 1040 pixels), rows 0..16 and 69..85 x columns 20..89 (frames 0, 1 and 2, 3: 1190 each) beside the
+#     centre of 3640; the ROI starts on an even column so that image column pj + W - padding = 185 (region column 90), the last
+#     one frames 0 and 2 contribute to, is in it.  Its whole region at step 1 has nine rectangles of 1365 to 14805 pixels.
+STEPPING_EXTRA = {
+    "stepping_mask_DF": dict(CONFIGS["stepping_DF"], mask="binary", seed=9931),
+    "stepping_NoDF":    dict(CONFIGS["stepping_DF"], df=False, assign="ref", tie=((-10, 1.0), (-10, 0.75)), seed=9932),
+    "stepping_s2":      dict(df=True, Nw=2, K=4, ms=3, H=150, W=190, assign="ref", force=0, path=4, pos=[(0, 0), (0, 40), (36, 0), (36, 40)],
+                             mk=dict(ROI=((3, 174, 2), (0, 217, 2))), seed=9933),
+}
+
+
+def config(name):
+    return CONFIGS[name] if name in CONFIGS else STEPPING_EXTRA[name]
+
+
 def padding(cfg):
     return cfg["Nw"] + cfg["ms"] + (8 if cfg.get("kernel") else 0)
 
@@ -168,8 +190,8 @@ _STACKS = {}
 def base_stack(name):
     """The scale-1 stack of a configuration, [K, H, W] (sample-stepping frames share a shape, so they stack too)."""
     if name not in _STACKS:
-        cfg = CONFIGS[name]
-        seed = 9000 + 37 * sorted(CONFIGS).index(name)
+        cfg = config(name)
+        seed = cfg["seed"] if "seed" in cfg else 9000 + 37 * sorted(CONFIGS).index(name)
         amp = cfg["ms"] - 2.4                                  # the 4 x 4 gather needs room inside the search box
         if cfg.get("pos"):
             fr = [make_stack(cfg["H"], cfg["W"], 1, cfg["ms"], df=cfg["df"], seed=seed + 17 * k, amplitude=amp, order=1) for k in range(cfg["K"])]
@@ -181,7 +203,7 @@ def base_stack(name):
 
 
 def mask_of(name):
-    cfg = CONFIGS[name]
+    cfg = config(name)
     kind = cfg.get("mask")
     if kind is None:
         return None
@@ -204,10 +226,10 @@ def frame_order(K):
     return np.roll(np.arange(K), 1)[::-1].copy()
 
 
-def run(ns, name, sam, ref, mask="cfg", subpx=-1, debug=True, mk=None, permute=False, timing=False):
-    """Match configuration `name` on the stacks with the model classes of `ns`; returns (result, model).  The forced
-    path and last_path only exist on the HIP side."""
-    cfg = CONFIGS[name]
+def build(ns, name, sam, ref, mask="cfg", subpx=-1, debug=True, permute=False):
+    """The model of configuration `name` on the stacks, with the model classes of `ns`.  The stacks may also be lists of
+    frames (device tensors: the model then borrows them)."""
+    cfg = config(name)
     if isinstance(mask, str):
         mask = mask_of(name)
     pos = cfg.get("pos")
@@ -221,8 +243,9 @@ def run(ns, name, sam, ref, mask="cfg", subpx=-1, debug=True, mk=None, permute=F
         kw["mask_list"] = mask
     if pos:
         kw["pos_list"] = [np.array(p) for p in pos]
-        sam, ref = [np.ascontiguousarray(f) for f in sam], [np.ascontiguousarray(f) for f in ref]
-        if mask is not None:
+        if isinstance(sam, np.ndarray):
+            sam, ref = [np.ascontiguousarray(f) for f in sam], [np.ascontiguousarray(f) for f in ref]
+        if isinstance(mask, np.ndarray):
             kw["mask_list"] = [np.ascontiguousarray(f) for f in mask]
     m = getattr(ns, model_name(cfg))(sam, ref, **kw)
     m.debug = debug
@@ -230,29 +253,49 @@ def run(ns, name, sam, ref, mask="cfg", subpx=-1, debug=True, mk=None, permute=F
     m.sub_pixel_mode = subpx
     if m._lib.is_hip:
         m._force = cfg["force"]
+    return m
+
+
+def kernel_abc(sh):
+    """The (a, b, c) maps of the kernel dark-field configuration for a region of shape `sh`"""
+    abc = np.zeros(tuple(sh) + (3,))
+    abc[..., 0], abc[..., 1], abc[..., 2] = 0.6, 0.1, 0.5
+    abc[..., 0] += np.linspace(0, 0.2, sh[1])[None, :]
+    return abc
+
+
+def match(m, name, mk=None, timing=False, path="cfg"):
+    """One match of a model of build() with the configuration's arguments (or `mk`); `path`: what last_path must say
+    (default: the configuration's, None: not checked)."""
+    cfg = config(name)
     mk = dict(cfg.get("mk", {}) if mk is None else mk, quiet=True)
     if cfg.get("kernel"):
         s0, s1 = m._convert_ROI_slice(None, mk.get("step"))
-        sh = m._counts(s0, s1)
-        abc = np.zeros(sh + (3,))
-        abc[..., 0], abc[..., 1], abc[..., 2] = 0.6, 0.1, 0.5
-        abc[..., 0] += np.linspace(0, 0.2, sh[1])[None, :]
-        mk["abc"] = abc
+        mk["abc"] = kernel_abc(m._counts(s0, s1))
     if timing:
         m._lib.timing_enable(m._handle, 1)
     out = m.match(**mk)
     out["window"] = m.window
-    if timing:                                                    # which kernels the match launched
+    if timing:                                                    # which kernels the match launched, and how often
         import ctypes
         m._lib.timing_enable(m._handle, 0)
-        m.launched = set()
+        m.launch_counts = {}
         for q in range(m._lib.timing_collect(m._handle)):
             nm, tot, cnt = ctypes.c_char_p(), ctypes.c_double(), ctypes.c_int()
             m._lib.timing_read(m._handle, q, ctypes.byref(nm), ctypes.byref(tot), ctypes.byref(cnt))
-            m.launched.add(nm.value.decode())
-    if m._lib.is_hip:
-        assert m._lib.last_path(m._handle) == cfg["path"], "%s ran on path %d, not %d" % (name, m._lib.last_path(m._handle), cfg["path"])
-    return out, m
+            m.launch_counts[nm.value.decode()] = cnt.value
+        m.launched = set(m.launch_counts)
+    if m._lib.is_hip and path is not None:
+        want = cfg["path"] if path == "cfg" else path
+        assert m._lib.last_path(m._handle) == want, "%s ran on path %d, not %d" % (name, m._lib.last_path(m._handle), want)
+    return out
+
+
+def run(ns, name, sam, ref, mask="cfg", subpx=-1, debug=True, mk=None, permute=False, timing=False):
+    """Match configuration `name` on the stacks with the model classes of `ns`; returns (result, model).  The forced
+    path and last_path only exist on the HIP side."""
+    m = build(ns, name, sam, ref, mask=mask, subpx=subpx, debug=debug, permute=permute)
+    return match(m, name, mk=mk, timing=timing), m
 
 
 def label(name, regime):
