@@ -13,10 +13,8 @@ reference's own build is one of the sides, `f` of failed pixels is not compared,
 reference returns an uninitialised value there).
 """
 import ctypes
-import importlib.util
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -24,49 +22,10 @@ import pytest
 from conftest import REPO, assert_parity
 
 import ddf_expect as DE
+from nativelibs import assert_claimed, build_all as _build, declared as _declared, exported, kernel_keys
 
 DDF_LIB = os.path.join(REPO, "umpa_amd", "libumpa_ddf.so")
-FAMILIES = ("ddf_blur_kernel", "ddf_fold_kernel")
 ILLPOSED = 0.012
-
-
-def _tool(name):
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    try:
-        return __import__(name)
-    finally:
-        sys.path.pop(0)
-
-
-def exported(lib):
-    """the defined dynamic symbols of a shared library"""
-    kc = _tool("kernel_coverage")
-    out = kc._run([kc.llvm_tool("llvm-readelf"), "--dyn-syms", "--wide", lib])
-    names = set()
-    for line in out.splitlines():
-        f = line.split(None, 7)
-        if len(f) == 8 and f[6] != "UND" and f[3] in ("FUNC", "OBJECT"):
-            names.add(f[7].split("@")[0].strip())
-    return names
-
-
-def kernel_keys(lib):
-    kc = _tool("kernel_coverage")
-    return [re.sub(r"^void ", "", s).split("(", 1)[0].split("::", 1)[-1] for s in kc.kernel_symbols(lib)]
-
-
-def _build():
-    import __graft_entry__ as g
-    libs = (g.HIP_LIB, g.GRID_LIB, g.UNWARP_LIB, g.REGISTER_LIB, g.INTEGRATE_LIB, g.DDF_LIB)
-    if not all(os.path.exists(p) for p in libs):
-        g.build()
-    return g
-
-
-def _declared():
-    hdr = open(os.path.join(REPO, "include", "umpa_ddf.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(umpa_ddf_[a-z_0-9]+)\s*\(", hdr)))
 
 
 # ----------------------------------------------------------------------------- 1. the library builds
@@ -75,7 +34,7 @@ def test_build_produces_the_ddf_library_with_the_declared_symbols():
     g = _build()
     assert g.DDF_LIB == DDF_LIB and os.path.exists(DDF_LIB)
     from umpa_amd import _lib
-    declared = _declared()
+    declared = _declared("umpa_ddf.h", "umpa_ddf_")
     assert declared == sorted("umpa_ddf_" + s for s in _lib.DDF_SYMBOLS) and len(declared) == 4
     own = sorted(n for n in exported(DDF_LIB) if n.startswith("umpa"))
     assert own == declared, own                                       # its C ABI and nothing else of its own
@@ -90,28 +49,11 @@ def test_build_produces_the_ddf_library_with_the_declared_symbols():
     assert (DE.TAPS, DE.HALF) == (_lib.DDF_TAPS, _lib.DDF_HALF)
 
 
-def test_the_other_libraries_hold_none_of_its_kernels_or_symbols():
-    g = _build()
-    for lib in (g.HIP_LIB, g.GRID_LIB, g.UNWARP_LIB, g.REGISTER_LIB, g.INTEGRATE_LIB):
-        assert not [n for n in exported(lib) if n.startswith("umpa_ddf")], lib
-        assert not [k for k in kernel_keys(lib) if k.split("<", 1)[0] in FAMILIES], lib
-    assert all(k.split("<", 1)[0] in FAMILIES for k in kernel_keys(DDF_LIB))
-
-
 def test_every_ddf_kernel_is_claimed_by_a_gpu_test():
     _build()
     syms = kernel_keys(DDF_LIB)
     assert sorted(syms) == ["ddf_blur_kernel<false>", "ddf_blur_kernel<true>", "ddf_fold_kernel"], syms
-    spec = importlib.util.spec_from_file_location("_ddf_gpu", os.path.join(REPO, "tests", "test_hip_ddf.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    claimed = set()
-    for names in mod.REACHES.values():
-        claimed |= set(names)
-    orphans = [s for s in syms if s not in claimed]
-    assert not orphans, "kernels of libumpa_ddf.so no test of tests/test_hip_ddf.py claims: %s" % orphans
-    stale = sorted(claimed - set(syms))
-    assert not stale, "REACHES names kernels the library does not have: %s" % stale
+    mod = assert_claimed(syms, "ddf")
     for test in mod.REACHES:
         assert hasattr(mod, test.split("::")[1]), test
 

@@ -3,10 +3,7 @@ The exhaustive grid search and the cost volume, what can be checked without a GP
 (tests/grid_expect.py), the admissibility of their inputs, and the second library's build.
 """
 import ctypes
-import importlib.util
 import os
-import re
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +11,7 @@ import pytest
 from conftest import REPO, Case
 
 import grid_expect as GE
+from nativelibs import assert_claimed, build_all as _build, declared, exported, kernel_keys
 
 GRID_LIB = os.path.join(REPO, "umpa_amd", "libumpa_grid.so")
 FAMILIES = ("grid_min_kernel", "cost_volume_kernel")
@@ -111,73 +109,22 @@ def test_gpu_inputs_have_few_near_ties(name, kind, assign):
 
 # ----------------------------------------------------------------------------- 3. the library builds
 
-def _declared():
-    hdr = open(os.path.join(REPO, "include", "umpa_grid.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(umpa_grid_[a-z_0-9]+)\s*\(", hdr)))
-
-
-def _build():
-    import __graft_entry__ as g
-    if not (os.path.exists(GRID_LIB) and os.path.exists(g.HIP_LIB)):
-        g.build()
-
-
-def _gpu_test_module():
-    spec = importlib.util.spec_from_file_location("_grid_gpu", os.path.join(REPO, "tests", "test_hip_grid.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_grid_library_builds_and_its_kernels_are_claimed():
     _build()
     assert os.path.exists(GRID_LIB)
     from umpa_amd import _lib
-    assert _declared() == sorted("umpa_grid_" + s for s in _lib.GRID_SYMBOLS) and len(_declared()) >= 2
+    assert declared("umpa_grid.h", "umpa_grid_") == sorted("umpa_grid_" + s for s in _lib.GRID_SYMBOLS) and len(declared("umpa_grid.h", "umpa_grid_")) >= 2
     _lib.hip()
     lib = ctypes.CDLL(GRID_LIB)
-    for name in _declared():
+    for name in declared("umpa_grid.h", "umpa_grid_"):
         assert hasattr(lib, name), name
     assert _lib.grid().path == GRID_LIB
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    try:
-        import kernel_coverage
-    finally:
-        sys.path.pop(0)
-    syms = []
-    for s in kernel_coverage.kernel_symbols(GRID_LIB):
-        key = re.sub(r"^void ", "", s).split("(", 1)[0].split("::", 1)[-1]
-        if key.split("<", 1)[0] in FAMILIES:
-            syms.append(key)
+    syms = [k for k in kernel_keys(GRID_LIB) if k.split("<", 1)[0] in FAMILIES]
     assert {s.split("<", 1)[0] for s in syms} == set(FAMILIES), syms
-    reaches = _gpu_test_module().REACHES
-    claimed = set()
-    for names in reaches.values():
-        claimed |= set(names)
-    orphans = [s for s in syms if s not in claimed]
-    assert not orphans, "kernels of libumpa_grid.so no test of tests/test_hip_grid.py claims: %s" % orphans
-    stale = sorted(claimed - set(syms))
-    assert not stale, "REACHES names kernels the library does not have: %s" % stale
+    assert_claimed(syms, "grid")
 
 
 # ----------------------------------------------------------------------------- 4. the main library: the hook, nothing else
-
-def exported(lib):
-    """the defined dynamic symbols of a shared library"""
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    try:
-        import kernel_coverage
-    finally:
-        sys.path.pop(0)
-    out = kernel_coverage._run([kernel_coverage.llvm_tool("llvm-readelf"), "--dyn-syms", "--wide", lib])
-    names = set()
-    for line in out.splitlines():
-        f = line.split(None, 7)
-        if len(f) == 8 and f[6] != "UND" and f[3] in ("FUNC", "OBJECT"):
-            names.add(f[7].split("@")[0].strip())
-    return names
-
 
 def test_main_library_exports_the_consumer_setter_and_no_new_public_symbol():
     _build()
@@ -191,4 +138,4 @@ def test_main_library_exports_the_consumer_setter_and_no_new_public_symbol():
     assert "umpa_hipx" not in hdr and "consumer" not in hdr
     # the grid library exports its C ABI and nothing else of its own
     own = sorted(n for n in exported(GRID_LIB) if n.startswith("umpa"))
-    assert own == _declared(), own
+    assert own == declared("umpa_grid.h", "umpa_grid_"), own

@@ -27,6 +27,7 @@ REACHES = {
     "test_hip_ddf.py::test_blur_within_bound": [BLUR_V, BLUR_S],
     "test_hip_ddf.py::test_blur_is_bit_identical_on_repetition_and_between_host_and_device": [BLUR_V, BLUR_S],
     "test_hip_ddf.py::test_nan_reaches_exactly_its_footprint": [BLUR_V, BLUR_S],
+    "test_hip_ddf.py::test_blur_of_more_frames_than_one_launch_takes": [BLUR_V],
     "test_hip_ddf.py::test_one_candidate": [BLUR_V, FOLD],
     "test_hip_ddf.py::test_sequence_of_candidates_on_one_searcher": [BLUR_V, FOLD],
     "test_hip_ddf.py::test_fold_of_a_search_equals_the_numpy_fold": [FOLD],
@@ -101,6 +102,32 @@ def test_blur_is_bit_identical_on_repetition_and_between_host_and_device(ddf):
     got = ddf.blur_frames(x, abc)
     np.testing.assert_array_equal(got[34], ddf.blur_frames(x[34], abc))
     np.testing.assert_array_equal(got[3], ddf.blur_frames(x[3:4], abc)[0])
+
+
+def test_blur_of_more_frames_than_one_launch_takes(ddf):
+    """33 frames, one more than UMPA_DDF_MAX_FRAMES: the host-array call uploads, blurs and downloads them in two rounds, the
+    device call launches twice.  The smallest frame the 16-byte kernel admits (17 x 18: two interior pixels), an
+    anisotropic kernel, every frame of both calls within the bound of test_blur_within_bound."""
+    import torch
+    from umpa_amd import _lib
+    K, abc = _lib.DDF_MAX_FRAMES + 1, DE.BLUR_KERNELS[2]
+    assert K == 33 and abc[0] != abc[2] and abc[1] != 0
+    x = _frames((K, 17, 18), 4)
+    g = ddf.gaussian_kernel(*abc)
+    host = ddf.blur_frames(x, abc)
+    dev = ddf.blur_frames(torch.from_numpy(x).cuda(), abc)
+    assert host.shape == x.shape and dev.is_cuda and tuple(dev.shape) == x.shape
+    dev = dev.cpu().numpy()
+    inner = np.zeros((17, 18), dtype=bool)
+    inner[8, 8:10] = True
+    for k in range(K):
+        want, bound = DE.blur_exact(x[k], g)
+        assert (bound[inner] > 0).all()
+        for name, got in (("host", host[k]), ("device", dev[k])):
+            np.testing.assert_array_equal(got[~inner], x[k][~inner], err_msg="%s frame %d" % (name, k))
+            err = np.abs(got.astype(np.longdouble) - want)
+            assert (err[inner] <= bound[inner]).all(), "%s frame %d: %.3f of the bound" % (name, k, float((err[inner] / bound[inner]).max()))
+            assert (got[inner] != x[k][inner]).all()                  # blurred, not copied
 
 
 @pytest.mark.parametrize("shape,at", [((40, 70), (20, 33)), ((40, 70), (3, 66)), ((41, 71), (20, 33)), ((41, 71), (37, 2))],

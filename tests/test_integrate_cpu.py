@@ -10,10 +10,8 @@ tests/golden/make_golden_integrate.py and checked here against a live dense solv
 """
 import ctypes
 import importlib
-import importlib.util
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -21,50 +19,9 @@ import pytest
 from conftest import REPO
 
 import integrate_expect as E
+from nativelibs import assert_claimed, build_all as _build, declared as _declared, exported, kernel_keys
 
 INTEGRATE_LIB = os.path.join(REPO, "umpa_amd", "libumpa_integrate.so")
-KERNELS = ["integrate_%s_kernel" % k for k in (
-    "weights", "diag", "rhs", "coarsen", "sweep0", "sweep", "restrict", "prolong", "jacobi", "tail",
-    "apply_dot", "update", "residual", "dot", "direction", "gauge", "output", "scalar")]
-
-
-def _tool(name):
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    try:
-        return __import__(name)
-    finally:
-        sys.path.pop(0)
-
-
-def _build():
-    import __graft_entry__ as g
-    libs = (g.HIP_LIB, g.GRID_LIB, g.UNWARP_LIB, g.REGISTER_LIB, g.INTEGRATE_LIB)
-    if not all(os.path.exists(p) for p in libs):
-        g.build()
-    return g
-
-
-def _declared():
-    hdr = open(os.path.join(REPO, "include", "umpa_integrate.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(umpa_integrate_[a-z_0-9]+)\s*\(", hdr)))
-
-
-def exported(lib):
-    kc = _tool("kernel_coverage")
-    out = kc._run([kc.llvm_tool("llvm-readelf"), "--dyn-syms", "--wide", lib])
-    names = set()
-    for line in out.splitlines():
-        f = line.split(None, 7)
-        if len(f) == 8 and f[6] != "UND" and f[3] in ("FUNC", "OBJECT"):
-            names.add(f[7].split("@")[0].strip())
-    return names
-
-
-def kernel_keys(lib):
-    kc = _tool("kernel_coverage")
-    return [re.sub(r"^void ", "", s).split("(", 1)[0].split("::", 1)[-1] for s in kc.kernel_symbols(lib)]
-
 
 def _module():
     return importlib.import_module("umpa_amd.integrate")
@@ -76,7 +33,7 @@ def test_build_produces_the_integrate_library_with_the_declared_symbols():
     g = _build()
     assert g.INTEGRATE_LIB == INTEGRATE_LIB and os.path.exists(INTEGRATE_LIB)
     from umpa_amd import _lib
-    declared = _declared()
+    declared = _declared("umpa_integrate.h", "umpa_integrate_")
     assert declared == sorted("umpa_integrate_" + s for s in _lib.INTEGRATE_SYMBOLS) and len(declared) == 3
     own = sorted(n for n in exported(INTEGRATE_LIB) if n.startswith("umpa"))
     assert own == declared, own                                       # its C ABI and nothing else of its own
@@ -96,31 +53,10 @@ def test_build_produces_the_integrate_library_with_the_declared_symbols():
         assert float(re.search(r"constexpr \w+ %s = ([0-9.]+);" % name, src).group(1)) == val, name
 
 
-def test_the_other_libraries_export_what_they_exported():
-    g = _build()
-    from umpa_amd import _lib
-    for lib, prefix, syms in [(g.HIP_LIB, "umpa_hip_", _lib.HIP_SYMBOLS), (g.GRID_LIB, "umpa_grid_", _lib.GRID_SYMBOLS),
-                              (g.UNWARP_LIB, "umpa_unwarp_", _lib.UNWARP_SYMBOLS), (g.REGISTER_LIB, "umpa_register_", _lib.REGISTER_SYMBOLS)]:
-        names = exported(lib)
-        assert sorted(n for n in names if n.startswith(prefix)) == sorted(prefix + s for s in syms), lib
-        assert not [n for n in names if n.startswith("umpa_integrate")], lib
-        assert not [k for k in kernel_keys(lib) if k.startswith("integrate_")], lib
-    assert sorted(kernel_keys(INTEGRATE_LIB)) == sorted(KERNELS)
-
-
 def test_every_integrate_kernel_is_claimed_by_a_gpu_test():
     _build()
     syms = kernel_keys(INTEGRATE_LIB)
-    spec = importlib.util.spec_from_file_location("_integrate_gpu", os.path.join(REPO, "tests", "test_hip_integrate.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    claimed = set()
-    for names in mod.REACHES.values():
-        claimed |= set(names)
-    orphans = [s for s in syms if s not in claimed]
-    assert not orphans, "kernels of libumpa_integrate.so no test of tests/test_hip_integrate.py claims: %s" % orphans
-    stale = sorted(claimed - set(syms))
-    assert not stale, "REACHES names kernels the library does not have: %s" % stale
+    mod = assert_claimed(syms, "integrate")
     for test in mod.REACHES:
         assert hasattr(mod, test.split("::")[1]), test
 

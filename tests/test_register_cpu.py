@@ -4,10 +4,8 @@ tests use (tests/register_expect.py) against the reference's recorded results (t
 logic of umpa_amd.register (fit, overlap, position solver), the argument errors and the library's error without a GPU.
 """
 import ctypes
-import importlib.util
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -15,48 +13,10 @@ import pytest
 from conftest import REPO
 
 import register_expect as RE
+from nativelibs import assert_claimed, build_all as _build, declared as _declared, exported, kernel_keys
 
 REGISTER_LIB = os.path.join(REPO, "umpa_amd", "libumpa_register.so")
-FAMILIES = ("register_tile_kernel", "register_norm_kernel", "register_reduce_kernel")
 S8 = (8, 8)
-
-
-def _tool(name):
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    try:
-        return __import__(name)
-    finally:
-        sys.path.pop(0)
-
-
-def _build():
-    import __graft_entry__ as g
-    if not (os.path.exists(REGISTER_LIB) and os.path.exists(g.HIP_LIB) and os.path.exists(g.GRID_LIB) and os.path.exists(g.UNWARP_LIB)):
-        g.build()
-    return g
-
-
-def _declared():
-    hdr = open(os.path.join(REPO, "include", "umpa_register.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(umpa_register_[a-z_0-9]+)\s*\(", hdr)))
-
-
-def exported(lib):
-    """the defined dynamic symbols of a shared library"""
-    kc = _tool("kernel_coverage")
-    out = kc._run([kc.llvm_tool("llvm-readelf"), "--dyn-syms", "--wide", lib])
-    names = set()
-    for line in out.splitlines():
-        f = line.split(None, 7)
-        if len(f) == 8 and f[6] != "UND" and f[3] in ("FUNC", "OBJECT"):
-            names.add(f[7].split("@")[0].strip())
-    return names
-
-
-def kernel_keys(lib):
-    kc = _tool("kernel_coverage")
-    return [re.sub(r"^void ", "", s).split("(", 1)[0].split("::", 1)[-1] for s in kc.kernel_symbols(lib)]
 
 
 # ----------------------------------------------------------------------------- 1. the library builds
@@ -65,7 +25,7 @@ def test_build_produces_the_register_library_with_the_declared_symbols():
     g = _build()
     assert g.REGISTER_LIB == REGISTER_LIB and os.path.exists(REGISTER_LIB)
     from umpa_amd import _lib
-    declared = _declared()
+    declared = _declared("umpa_register.h", "umpa_register_")
     assert declared == sorted("umpa_register_" + s for s in _lib.REGISTER_SYMBOLS) and len(declared) == 2
     own = sorted(n for n in exported(REGISTER_LIB) if n.startswith("umpa"))
     assert own == declared, own                                       # its C ABI and nothing else of its own
@@ -80,34 +40,11 @@ def test_build_produces_the_register_library_with_the_declared_symbols():
     assert int(re.search(r"#define UMPA_REGISTER_F_SHARED_W (\d+)", hdr).group(1)) == _lib.REGISTER_F_SHARED_W
 
 
-def test_the_other_libraries_export_what_they_exported():
-    g = _build()
-    from umpa_amd import _lib
-    for lib, prefix, syms in [(g.HIP_LIB, "umpa_hip_", _lib.HIP_SYMBOLS), (g.GRID_LIB, "umpa_grid_", _lib.GRID_SYMBOLS),
-                              (g.UNWARP_LIB, "umpa_unwarp_", _lib.UNWARP_SYMBOLS)]:
-        names = exported(lib)
-        assert sorted(n for n in names if n.startswith(prefix)) == sorted(prefix + s for s in syms), lib
-        assert not [n for n in names if n.startswith("umpa_register")], lib
-    # and their kernels: none of the registration kernels got into them, none of theirs into the new library
-    for lib in (g.HIP_LIB, g.GRID_LIB, g.UNWARP_LIB):
-        assert not [k for k in kernel_keys(lib) if k.split("<", 1)[0] in FAMILIES], lib
-    assert all(k.split("<", 1)[0] in FAMILIES for k in kernel_keys(REGISTER_LIB))
-
-
 def test_every_register_kernel_is_claimed_by_a_gpu_test():
     _build()
     syms = kernel_keys(REGISTER_LIB)
     assert len(syms) == 3 * 2 * 2 + 3 + 1, syms                       # dtype x weighted x boundary, the norms, the reduction
-    spec = importlib.util.spec_from_file_location("_register_gpu", os.path.join(REPO, "tests", "test_hip_register.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    claimed = set()
-    for names in mod.REACHES.values():
-        claimed |= set(names)
-    orphans = [s for s in syms if s not in claimed]
-    assert not orphans, "kernels of libumpa_register.so no test of tests/test_hip_register.py claims: %s" % orphans
-    stale = sorted(claimed - set(syms))
-    assert not stale, "REACHES names kernels the library does not have: %s" % stale
+    mod = assert_claimed(syms, "register")
     for test in mod.REACHES:
         assert hasattr(mod, test.split("::")[1]), test
 

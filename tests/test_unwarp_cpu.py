@@ -4,10 +4,7 @@ the main library, the host logic of umpa_amd.unwarp, the expectation the GPU tes
 pinned points, and the farm's hand-over of the map to its workers.
 """
 import ctypes
-import importlib.util
 import os
-import re
-import sys
 
 import numpy as np
 import pytest
@@ -15,42 +12,10 @@ import pytest
 from conftest import REPO
 
 import unwarp_expect as UE
+from nativelibs import assert_claimed, build_all as _build, declared as _declared, exported, kernel_keys
 
 UNWARP_LIB = os.path.join(REPO, "umpa_amd", "libumpa_unwarp.so")
 FAMILY = "unwarp_kernel"
-
-
-def _tool(name):
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    try:
-        return __import__(name)
-    finally:
-        sys.path.pop(0)
-
-
-def _build():
-    import __graft_entry__ as g
-    if not (os.path.exists(UNWARP_LIB) and os.path.exists(g.HIP_LIB)):
-        g.build()
-    return g
-
-
-def _declared():
-    hdr = open(os.path.join(REPO, "include", "umpa_unwarp.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(umpa_unwarp_[a-z_0-9]+)\s*\(", hdr)))
-
-
-def exported(lib):
-    """the defined dynamic symbols of a shared library"""
-    kc = _tool("kernel_coverage")
-    out = kc._run([kc.llvm_tool("llvm-readelf"), "--dyn-syms", "--wide", lib])
-    names = set()
-    for line in out.splitlines():
-        f = line.split(None, 7)
-        if len(f) == 8 and f[6] != "UND" and f[3] in ("FUNC", "OBJECT"):
-            names.add(f[7].split("@")[0].strip())
-    return names
 
 
 # ----------------------------------------------------------------------------- 1. the library builds
@@ -59,7 +24,7 @@ def test_build_produces_the_unwarp_library_with_the_declared_symbols():
     g = _build()
     assert g.UNWARP_LIB == UNWARP_LIB and os.path.exists(UNWARP_LIB)
     from umpa_amd import _lib
-    declared = _declared()
+    declared = _declared("umpa_unwarp.h", "umpa_unwarp_")
     assert declared == sorted("umpa_unwarp_" + s for s in _lib.UNWARP_SYMBOLS) and len(declared) == 5
     own = sorted(n for n in exported(UNWARP_LIB) if n.startswith("umpa"))
     assert own == declared, own                                       # its C ABI and nothing else of its own
@@ -83,23 +48,9 @@ def test_main_library_exports_the_stage_filter_setter_and_no_new_public_symbol()
 
 def test_every_unwarp_kernel_is_claimed_by_a_gpu_test():
     _build()
-    kc = _tool("kernel_coverage")
-    syms = []
-    for s in kc.kernel_symbols(UNWARP_LIB):
-        key = re.sub(r"^void ", "", s).split("(", 1)[0].split("::", 1)[-1]
-        if key.split("<", 1)[0] == FAMILY:
-            syms.append(key)
+    syms = [k for k in kernel_keys(UNWARP_LIB) if k.split("<", 1)[0] == FAMILY]
     assert len(syms) == 6, syms                                       # three raw dtypes x two interpolation kinds
-    spec = importlib.util.spec_from_file_location("_unwarp_gpu", os.path.join(REPO, "tests", "test_hip_unwarp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    claimed = set()
-    for names in mod.REACHES.values():
-        claimed |= set(names)
-    orphans = [s for s in syms if s not in claimed]
-    assert not orphans, "kernels of libumpa_unwarp.so no test of tests/test_hip_unwarp.py claims: %s" % orphans
-    stale = sorted(claimed - set(syms))
-    assert not stale, "REACHES names kernels the library does not have: %s" % stale
+    assert_claimed(syms, "unwarp")
 
 
 # ----------------------------------------------------------------------------- 2. host logic

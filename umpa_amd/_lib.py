@@ -21,14 +21,7 @@ F_DEVICE_IO, F_FORCE_DIRECT, F_FORCE_TILED, F_PLANAR, F_REUSE_REF_MAPS, F_USE_ST
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _dpp = C.POINTER(_dp)
-
-# every symbol include/umpa_hip.h declares (checked by tests/test_cabi_symbols.py)
-HIP_SYMBOLS = [
-    "device_count", "last_error", "version", "create", "destroy", "set_window", "set_subpx",
-    "set_reference_shift", "coverage", "coverage_region", "cost", "min", "match_region",
-    "spmin", "spmin_quad", "timing_enable", "timing_collect", "timing_read", "timing_fma", "last_path", "host_alloc", "host_free", "host_trim", "stage_sample", "wait", "set_rows_callback", "host_register", "host_unregister",
-    "update_frames", "correct_bad_pixels", "last_stats",
-]
+_int, _vp, _dbl = C.c_int, C.c_void_p, C.c_double
 
 
 class NativeError(RuntimeError):
@@ -39,70 +32,25 @@ def _ptr(a, typ):
     return a.ctypes.data_as(typ) if a is not None else None
 
 
-class Native:
-    """One loaded library + prefix."""
+class Library:
+    """One loaded shared library: every function of ``table`` (``{name: (restype, argtypes)}``, exported as
+    ``prefix + name``) is an attribute.  A table is the whole C ABI of its header: its keys are that library's ``*_SYMBOLS``."""
 
-    def __init__(self, path, prefix, is_hip):
+    def __init__(self, path, prefix, table):
         if not os.path.exists(path):
             raise NativeError(
                 "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU fallback)" % path)
-        self.path, self.prefix, self.is_hip = path, prefix, is_hip
+        self.path, self.prefix = path, prefix
         self.lib = C.CDLL(path)
-        f = self._f
-        create_args = [C.c_int, C.c_int, _ip, _dpp, _dpp, _dpp, _ip, C.c_int, _dp, C.c_int, C.c_int]
-        if is_hip:
-            create_args += [C.c_int, C.c_int]
-        f("create", C.c_void_p, create_args)
-        f("destroy", None, [C.c_void_p])
-        f("set_window", C.c_int if is_hip else None, [C.c_void_p, _dp, C.c_int])
-        f("set_subpx", C.c_int if is_hip else None, [C.c_void_p, C.c_int])
-        f("set_reference_shift", C.c_int if is_hip else None, [C.c_void_p, C.c_int])
-        f("coverage", C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int])
-        f("cost", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp])
-        f("min", C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip])
-        mr = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-        mr += [C.c_int, C.c_void_p] if is_hip else [C.c_int]
-        f("match_region", C.c_int if is_hip else None, mr)
-        if is_hip:
-            f("device_count", C.c_int, [])
-            f("last_error", C.c_char_p, [])
-            f("version", C.c_char_p, [])
-            f("coverage_region", C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_dp])
-            f("spmin", C.c_int, [C.c_int, _dp, _dp, _dp])
-            f("spmin_quad", C.c_int, [C.c_int, _dp, _dp, _dp])
-            f("timing_enable", C.c_int, [C.c_void_p, C.c_int])
-            f("timing_collect", C.c_int, [C.c_void_p])
-            f("timing_read", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), _dp, _ip])
-            f("timing_fma", C.c_int, [C.c_void_p, C.c_int, _dp])
-            f("host_alloc", C.c_void_p, [C.c_size_t])
-            f("host_free", None, [C.c_void_p])
-            f("host_trim", None, [])
-            f("stage_sample", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
-            f("wait", C.c_int, [C.c_void_p])
-            f("set_rows_callback", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
-            f("host_register", C.c_int, [C.c_void_p, C.c_size_t])
-            f("host_unregister", C.c_int, [C.c_void_p])
-            f("last_path", C.c_int, [C.c_void_p])
-            f("last_stats", C.c_int, [C.c_void_p, _dp])
-            f("update_frames", C.c_int, [C.c_void_p, _dpp, _dpp])
-            f("correct_bad_pixels", C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int,
-                                              C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p])
-        else:
-            f("spmin", C.c_double, [_dp, _dp])
-            f("spmin_quad", C.c_double, [_dp, _dp])
-            f("max_threads", C.c_int, [])
-
-    def _f(self, name, restype, argtypes):
-        fn = getattr(self.lib, self.prefix + name)
-        fn.restype, fn.argtypes = restype, argtypes
-        setattr(self, name, fn)
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(self.lib, prefix + name)
+            fn.restype, fn.argtypes = restype, argtypes
+            setattr(self, name, fn)
 
     def error(self):
-        if self.is_hip:
-            return (self.last_error() or b"").decode()
-        return ""
+        last = getattr(self, "last_error", None)                     # (the CPU checkers keep no error text)
+        return (last() or b"").decode() if last else ""
 
     def check(self, rc, what):
         if rc is not None and rc < 0:
@@ -110,7 +58,65 @@ class Native:
         return rc
 
 
-_hip = None
+def _model_abi(is_hip):
+    """``include/umpa_hip.h`` (``is_hip``), or the call shapes the CPU checkers share with it."""
+    create = [_int, _int, _ip, _dpp, _dpp, _dpp, _ip, _int, _dp, _int, _int] + ([_int, _int] if is_hip else [])
+    region = [_vp] + [_int] * 6 + [_vp, _int, _vp, _vp, _vp, _dbl, _vp, _vp, _vp] + ([_int, _vp] if is_hip else [_int])
+    status = _int if is_hip else None
+    abi = {
+        "create": (_vp, create),
+        "destroy": (None, [_vp]),
+        "set_window": (status, [_vp, _dp, _int]),
+        "set_subpx": (status, [_vp, _int]),
+        "set_reference_shift": (status, [_vp, _int]),
+        "coverage": (_int, [_vp, _dp, _int, _int]),
+        "cost": (_int, [_vp, _int, _int, _int, _int, _dp]),
+        "min": (_int, [_vp, _int, _int, _dp, _dp, _dp, _dp, _ip]),
+        "match_region": (status, region),
+    }
+    if not is_hip:
+        abi.update({"spmin": (_dbl, [_dp, _dp]), "spmin_quad": (_dbl, [_dp, _dp]), "max_threads": (_int, [])})
+        return abi
+    abi.update({
+        "device_count": (_int, []),
+        "last_error": (C.c_char_p, []),
+        "version": (C.c_char_p, []),
+        "coverage_region": (_int, [_vp] + [_int] * 6 + [_dp]),
+        "spmin": (_int, [_int, _dp, _dp, _dp]),
+        "spmin_quad": (_int, [_int, _dp, _dp, _dp]),
+        "timing_enable": (_int, [_vp, _int]),
+        "timing_collect": (_int, [_vp]),
+        "timing_read": (_int, [_vp, _int, C.POINTER(C.c_char_p), _dp, _ip]),
+        "timing_fma": (_int, [_vp, _int, _dp]),
+        "host_alloc": (_vp, [C.c_size_t]),
+        "host_free": (None, [_vp]),
+        "host_trim": (None, []),
+        "stage_sample": (_int, [_vp, _vp, _int, _vp, _vp]),
+        "wait": (_int, [_vp]),
+        "set_rows_callback": (_int, [_vp, _vp, _vp, _int]),
+        "host_register": (_int, [_vp, C.c_size_t]),
+        "host_unregister": (_int, [_vp]),
+        "last_path": (_int, [_vp]),
+        "last_stats": (_int, [_vp, _dp]),
+        "update_frames": (_int, [_vp, _dpp, _dpp]),
+        "correct_bad_pixels": (_int, [_vp, _vp, C.c_long, _int, _int, _int, _dbl, _dbl, _int, _int, _int, _vp]),
+    })
+    return abi
+
+
+# every symbol include/umpa_hip.h declares (checked by tests/test_cabi_symbols.py)
+HIP_SYMBOLS = list(_model_abi(True))
+
+
+class Native(Library):
+    """One loaded library + prefix with the model ABI: ``libumpa_hip.so``, or a CPU checker of ``oracle/``."""
+
+    def __init__(self, path, prefix, is_hip):
+        Library.__init__(self, path, prefix, _model_abi(is_hip))
+        self.is_hip = is_hip
+
+
+_loaded = {}
 
 
 def _pin_hip_runtime():
@@ -132,240 +138,115 @@ def _pin_hip_runtime():
 
 def hip():
     """The product library.  Raises if it is not built; never substitutes anything else."""
-    global _hip
-    if _hip is None:
+    if "hip" not in _loaded:
         _pin_hip_runtime()
-        _hip = Native(HIP_LIB_PATH, "umpa_hip_", True)
-    return _hip
+        _loaded["hip"] = Native(HIP_LIB_PATH, "umpa_hip_", True)
+    return _loaded["hip"]
 
 
+def _satellite(name, table):
+    """``libumpa_<name>.so``, loaded at first use from ``<NAME>_LIB_PATH``, after the product library it links or works on.
+    Raises if it is not built."""
+    if name not in _loaded:
+        hip()
+        _loaded[name] = Library(globals()[name.upper() + "_LIB_PATH"], "umpa_%s_" % name, table)
+    return _loaded[name]
+
+
+# One table per satellite library: every symbol its header declares, with its signature.
+
+# include/umpa_grid.h: the exhaustive grid search and the cost volume, on models of libumpa_hip.so
 GRID_LIB_PATH = os.path.join(_HERE, "libumpa_grid.so")
-# every symbol include/umpa_grid.h declares
-GRID_SYMBOLS = ["match_region", "cost_volume", "last_error"]
-_grid = None
+_GRID_ABI = {
+    "match_region": (_int, _model_abi(True)["match_region"][1]),
+    "cost_volume": (_int, [_vp] + [_int] * 6 + [_vp] * 3 + [_int, _vp]),
+    "last_error": (C.c_char_p, []),
+}
+GRID_SYMBOLS = list(_GRID_ABI)
 
-
-class GridNative:
-    """``libumpa_grid.so`` (``include/umpa_grid.h``): the exhaustive grid search and the cost volume, on models of
-    ``libumpa_hip.so``."""
-
-    def __init__(self, path):
-        if not os.path.exists(path):
-            raise NativeError(
-                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(there is no CPU fallback)" % path)
-        self.path = path
-        self.lib = C.CDLL(path)
-        mr = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        self.match_region = self._f("match_region", C.c_int, mr)
-        self.cost_volume = self._f("cost_volume", C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p])
-        self.last_error = self._f("last_error", C.c_char_p, [])
-
-    def _f(self, name, restype, argtypes):
-        fn = getattr(self.lib, "umpa_grid_" + name)
-        fn.restype, fn.argtypes = restype, argtypes
-        return fn
-
-    def error(self):
-        return (self.last_error() or b"").decode()
-
-    def check(self, rc, what):
-        if rc is not None and rc < 0:
-            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
-        return rc
-
-
-def grid():
-    """The grid-search library, loaded at first use (after the product library it works on).  Raises if it is not built."""
-    global _grid
-    if _grid is None:
-        hip()
-        _grid = GridNative(GRID_LIB_PATH)
-    return _grid
-
-
+# include/umpa_unwarp.h: detector distortion correction, stand-alone and fused into stage_sample of models of libumpa_hip.so
 UNWARP_LIB_PATH = os.path.join(_HERE, "libumpa_unwarp.so")
-# every symbol include/umpa_unwarp.h declares
-UNWARP_SYMBOLS = ["map_create", "map_destroy", "frames", "attach", "last_error"]
-_unwarp = None
+_UNWARP_ABI = {
+    "map_create": (_vp, [_int, _int, C.POINTER(C.c_float), C.POINTER(C.c_float), _int, _int]),
+    "map_destroy": (None, [_vp]),
+    "frames": (_int, [_vp, _vp, _int, _int, _vp, _vp, _vp, _int, _vp]),
+    "attach": (_int, [_vp, _vp]),
+    "last_error": (C.c_char_p, []),
+}
+UNWARP_SYMBOLS = list(_UNWARP_ABI)
 
-
-class UnwarpNative:
-    """``libumpa_unwarp.so`` (``include/umpa_unwarp.h``): detector distortion correction, stand-alone and fused into
-    ``stage_sample`` of models of ``libumpa_hip.so``."""
-
-    def __init__(self, path):
-        if not os.path.exists(path):
-            raise NativeError(
-                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(there is no CPU fallback)" % path)
-        self.path = path
-        self.lib = C.CDLL(path)
-        self.map_create = self._f("map_create", C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int])
-        self.map_destroy = self._f("map_destroy", None, [C.c_void_p])
-        self.frames = self._f("frames", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
-        self.attach = self._f("attach", C.c_int, [C.c_void_p, C.c_void_p])
-        self.last_error = self._f("last_error", C.c_char_p, [])
-
-    def _f(self, name, restype, argtypes):
-        fn = getattr(self.lib, "umpa_unwarp_" + name)
-        fn.restype, fn.argtypes = restype, argtypes
-        return fn
-
-    def error(self):
-        return (self.last_error() or b"").decode()
-
-    def check(self, rc, what):
-        if rc is not None and rc < 0:
-            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
-        return rc
-
-
-def unwarp():
-    """The unwarp library, loaded at first use (after the product library it works on).  Raises if it is not built."""
-    global _unwarp
-    if _unwarp is None:
-        hip()
-        _unwarp = UnwarpNative(UNWARP_LIB_PATH)
-    return _unwarp
-
-
+# include/umpa_register.h: the sums of the registration distance over a box of shifts
 REGISTER_LIB_PATH = os.path.join(_HERE, "libumpa_register.so")
-# every symbol include/umpa_register.h declares
-REGISTER_SYMBOLS = ["sums", "last_error"]
 REGISTER_MAX_SHIFT = 32
 REGISTER_F_SHARED_A, REGISTER_F_SHARED_W = 256, 512
-_register = None
+_REGISTER_ABI = {
+    "sums": (_int, [_vp, _vp, _vp] + [_int] * 7 + [_vp] * 3 + [_int, _int, _vp]),
+    "last_error": (C.c_char_p, []),
+}
+REGISTER_SYMBOLS = list(_REGISTER_ABI)
 
-
-class RegisterNative:
-    """``libumpa_register.so`` (``include/umpa_register.h``): the sums of the registration distance over a box of shifts."""
-
-    def __init__(self, path):
-        if not os.path.exists(path):
-            raise NativeError(
-                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(there is no CPU fallback)" % path)
-        self.path = path
-        self.lib = C.CDLL(path)
-        self.sums = self._f("sums", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p])
-        self.last_error = self._f("last_error", C.c_char_p, [])
-
-    def _f(self, name, restype, argtypes):
-        fn = getattr(self.lib, "umpa_register_" + name)
-        fn.restype, fn.argtypes = restype, argtypes
-        return fn
-
-    def error(self):
-        return (self.last_error() or b"").decode()
-
-    def check(self, rc, what):
-        if rc is not None and rc < 0:
-            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
-        return rc
-
-
-def register():
-    """The registration library, loaded at first use (after the product library it links).  Raises if it is not built."""
-    global _register
-    if _register is None:
-        hip()
-        _register = RegisterNative(REGISTER_LIB_PATH)
-    return _register
-
-
+# include/umpa_integrate.h: weighted least-squares phase integration
 INTEGRATE_LIB_PATH = os.path.join(_HERE, "libumpa_integrate.so")
-# every symbol include/umpa_integrate.h declares
-INTEGRATE_SYMBOLS = ["solve", "vcycle", "last_error"]
 INTEGRATE_F_NO_TAIL, INTEGRATE_F_JACOBI, INTEGRATE_F_DEBUG = 256, 512, 1024
 INTEGRATE_CONVERGED, INTEGRATE_MAXITER, INTEGRATE_BREAKDOWN = 0, 1, 2
 INTEGRATE_CHECK_EVERY = 8
-_integrate = None
+_INTEGRATE_ABI = {
+    "solve": (_int, [_vp] * 3 + [_int] * 3 + [_dbl, _int, _dbl] + [_vp] * 4 + [_int, _int, _vp]),
+    "vcycle": (_int, [_vp] * 3 + [_int] * 4 + [_vp]),
+    "last_error": (C.c_char_p, []),
+}
+INTEGRATE_SYMBOLS = list(_INTEGRATE_ABI)
+
+# include/umpa_ddf.h: the whole-image blur and the candidate fold of the directional dark-field search
+DDF_LIB_PATH = os.path.join(_HERE, "libumpa_ddf.so")
+DDF_TAPS, DDF_HALF, DDF_MAX_FRAMES = 17, 8, 32
+_DDF_ABI = {
+    "kernel": (_int, [_dbl] * 3 + [_vp]),
+    "blur": (_int, [_vp, _vp] + [_int] * 3 + [_vp, _int, _int, _vp]),
+    "fold": (_int, [_int, C.c_longlong] + [_vp] * 11 + [_int, _int, _vp]),
+    "last_error": (C.c_char_p, []),
+}
+DDF_SYMBOLS = list(_DDF_ABI)
 
 
-class IntegrateNative:
-    """``libumpa_integrate.so`` (``include/umpa_integrate.h``): weighted least-squares phase integration."""
+def grid():
+    return _satellite("grid", _GRID_ABI)
 
-    def __init__(self, path):
-        if not os.path.exists(path):
-            raise NativeError(
-                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(there is no CPU fallback)" % path)
-        self.path = path
-        self.lib = C.CDLL(path)
-        self.solve = self._f("solve", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_double, C.c_int, C.c_double] + [C.c_void_p] * 4
-                             + [C.c_int, C.c_int, C.c_void_p])
-        self.vcycle = self._f("vcycle", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p])
-        self.last_error = self._f("last_error", C.c_char_p, [])
 
-    def _f(self, name, restype, argtypes):
-        fn = getattr(self.lib, "umpa_integrate_" + name)
-        fn.restype, fn.argtypes = restype, argtypes
-        return fn
+def unwarp():
+    return _satellite("unwarp", _UNWARP_ABI)
 
-    def error(self):
-        return (self.last_error() or b"").decode()
 
-    def check(self, rc, what):
-        if rc is not None and rc < 0:
-            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
-        return rc
+def register():
+    return _satellite("register", _REGISTER_ABI)
 
 
 def integrate():
-    """The integration library, loaded at first use (after the product library it links).  Raises if it is not built."""
-    global _integrate
-    if _integrate is None:
-        hip()
-        _integrate = IntegrateNative(INTEGRATE_LIB_PATH)
-    return _integrate
-
-
-DDF_LIB_PATH = os.path.join(_HERE, "libumpa_ddf.so")
-# every symbol include/umpa_ddf.h declares
-DDF_SYMBOLS = ["kernel", "blur", "fold", "last_error"]
-DDF_TAPS, DDF_HALF, DDF_MAX_FRAMES = 17, 8, 32
-_ddf = None
-
-
-class DdfNative:
-    """``libumpa_ddf.so`` (``include/umpa_ddf.h``): the whole-image blur and the candidate fold of the directional
-    dark-field search."""
-
-    def __init__(self, path):
-        if not os.path.exists(path):
-            raise NativeError(
-                "native library %s not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(there is no CPU fallback)" % path)
-        self.path = path
-        self.lib = C.CDLL(path)
-        self.kernel = self._f("kernel", C.c_int, [C.c_double] * 3 + [C.c_void_p])
-        self.blur = self._f("blur", C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p])
-        self.fold = self._f("fold", C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_void_p])
-        self.last_error = self._f("last_error", C.c_char_p, [])
-
-    def _f(self, name, restype, argtypes):
-        fn = getattr(self.lib, "umpa_ddf_" + name)
-        fn.restype, fn.argtypes = restype, argtypes
-        return fn
-
-    def error(self):
-        return (self.last_error() or b"").decode()
-
-    def check(self, rc, what):
-        if rc is not None and rc < 0:
-            raise NativeError("%s failed (%d): %s" % (what, rc, self.error()))
-        return rc
+    return _satellite("integrate", _INTEGRATE_ABI)
 
 
 def ddf():
-    """The dark-field search library, loaded at first use (after the product library it links).  Raises if it is not built."""
-    global _ddf
-    if _ddf is None:
-        hip()
-        _ddf = DdfNative(DDF_LIB_PATH)
-    return _ddf
+    return _satellite("ddf", _DDF_ABI)
+
+
+def device_io(*tensors):
+    """``(device index, stream handle)`` for a call on HIP tensors (``None`` entries are skipped): the tensors' device and
+    the caller's current stream on it.  They must be contiguous and on one HIP device."""
+    import torch
+    given = [t for t in tensors if t is not None]
+    for t in given:
+        if not t.is_contiguous() or not t.is_cuda or t.device != given[0].device:
+            raise ValueError("device arrays must be contiguous HIP tensors on one device")
+    d = given[0].device
+    return d.index if d.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(d).cuda_stream
+
+
+def host_device(device):
+    """The device index of a call on host arrays: ``device``, or the package's default for ``None``."""
+    if device is None:
+        from . import model
+        return model._default_device()
+    return int(device)
 
 
 ROWS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)       # umpa_hip_rows_fn

@@ -10,12 +10,10 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstdarg>
 #include <cstring>
-#include <string>
 
 #include "../../include/umpa_ddf.h"
+#include "umpa_host.h"
 
 namespace umpa {
 
@@ -149,34 +147,6 @@ using namespace umpa;
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-struct Scratch {                       // device memory of one call
-    void* p[12] = {};
-    ~Scratch() { for (void* q : p) if (q) (void)hipFree(q); }
-};
-
-int pick_device(const char* what, int device)
-{
-    const int ndev = umpa_hip_device_count();
-    if (ndev < 1) return fail(UMPA_HIP_E_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(UMPA_HIP_E_ARG, "device %d out of range (%d devices)", device, ndev);
-    const hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "%s: hipSetDevice(%d): %s", what, device, hipGetErrorString(e));
-    return 0;
-}
-
 // Up to UMPA_DDF_MAX_FRAMES device frames per launch.
 hipError_t launch_blur(const double* const* in, double* const* out, int K, int H, int W, const DdfCoef& coef, hipStream_t s)
 {
@@ -242,23 +212,21 @@ UMPA_DDF_API int umpa_ddf_blur(const double* const* in, double* const* out, int 
             if (a < b + n * 8 && b < a + n * 8) return fail(UMPA_HIP_E_ARG, "ddf: input frame %d and output frame %d overlap (in and out may not alias)", k, q);
         }
     }
-    int rc = pick_device("ddf", device);
-    if (rc < 0) return rc;
+    if (int rc = pick_device("ddf", device)) return rc;
     if (K == 0) return 0;
     DdfCoef coef;
     memcpy(coef.g, kern, sizeof(coef.g));
-    hipError_t e;
     if (flags & UMPA_HIP_F_DEVICE_IO) {
         hipStream_t s = (hipStream_t)stream;
-        if ((e = launch_blur(in, out, K, H, W, coef, s)) != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "ddf: launch of the blur: %s", hipGetErrorString(e));
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "ddf: blur: %s", hipGetErrorString(e));
+        HIPOK(launch_blur(in, out, K, H, W, coef, s), UMPA_HIP_E_LAUNCH, "ddf: launch of the blur");
+        HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "ddf: blur");
         return 0;
     }
     // host arrays: device copies of up to UMPA_DDF_MAX_FRAMES frames at a time, on the null stream
     const int chunk = K < UMPA_DDF_MAX_FRAMES ? K : UMPA_DDF_MAX_FRAMES;
-    Scratch S;
-    if ((e = hipMalloc(&S.p[0], n * 8 * chunk)) != hipSuccess) { S.p[0] = nullptr; return fail(UMPA_HIP_E_NOMEM, "ddf: device memory for %d frames: %s", chunk, hipGetErrorString(e)); }
-    if ((e = hipMalloc(&S.p[1], n * 8 * chunk)) != hipSuccess) { S.p[1] = nullptr; return fail(UMPA_HIP_E_NOMEM, "ddf: device memory for %d frames: %s", chunk, hipGetErrorString(e)); }
+    DeviceMem S;
+    HIPOK(S.alloc(0, n * 8 * chunk), UMPA_HIP_E_NOMEM, "ddf: device memory for %d frames", chunk);
+    HIPOK(S.alloc(1, n * 8 * chunk), UMPA_HIP_E_NOMEM, "ddf: device memory for %d frames", chunk);
     for (int k0 = 0; k0 < K; k0 += chunk) {
         const int nk = K - k0 < chunk ? K - k0 : chunk;
         const double* din[UMPA_DDF_MAX_FRAMES];
@@ -266,13 +234,11 @@ UMPA_DDF_API int umpa_ddf_blur(const double* const* in, double* const* out, int 
         for (int k = 0; k < nk; k++) {
             din[k] = (const double*)S.p[0] + (size_t)k * n;
             dout[k] = (double*)S.p[1] + (size_t)k * n;
-            if ((e = hipMemcpy((void*)din[k], in[k0 + k], n * 8, hipMemcpyHostToDevice)) != hipSuccess)
-                return fail(UMPA_HIP_E_DEVICE, "ddf: upload of frame %d: %s", k0 + k, hipGetErrorString(e));
+            HIPOK(hipMemcpy((void*)din[k], in[k0 + k], n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "ddf: upload of frame %d", k0 + k);
         }
-        if ((e = launch_blur(din, dout, nk, H, W, coef, nullptr)) != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "ddf: launch of the blur: %s", hipGetErrorString(e));
+        HIPOK(launch_blur(din, dout, nk, H, W, coef, nullptr), UMPA_HIP_E_LAUNCH, "ddf: launch of the blur");
         for (int k = 0; k < nk; k++)
-            if ((e = hipMemcpy(out[k0 + k], dout[k], n * 8, hipMemcpyDeviceToHost)) != hipSuccess)
-                return fail(UMPA_HIP_E_LAUNCH, "ddf: blur of frame %d: %s", k0 + k, hipGetErrorString(e));
+            HIPOK(hipMemcpy(out[k0 + k], dout[k], n * 8, hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "ddf: blur of frame %d", k0 + k);
     }
     return 0;
 }
@@ -286,36 +252,32 @@ UMPA_DDF_API int umpa_ddf_fold(int m, long long N, const double* f, const double
     if (m < 0) return fail(UMPA_HIP_E_ARG, "ddf: candidate number %d", m);
     if (N < 0 || N >= (1LL << 31) * 256) return fail(UMPA_HIP_E_ARG, "ddf: planes of %lld pixels", N);
     if (flags & ~UMPA_HIP_F_DEVICE_IO) return fail(UMPA_HIP_E_ARG, "ddf: fold takes UMPA_HIP_F_DEVICE_IO and no other flag");
-    int rc = pick_device("ddf", device);
-    if (rc < 0) return rc;
+    if (int rc = pick_device("ddf", device)) return rc;
     if (N == 0) return 0;
     const size_t n = (size_t)N;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    hipError_t e;
     if (flags & UMPA_HIP_F_DEVICE_IO) {
         hipStream_t s = (hipStream_t)stream;
         hipLaunchKernelGGL(ddf_fold_kernel, grid, block, 0, s, m, n, f, T, dx, dy, err, best_f, best_T, best_dx, best_dy, index, best_err);
-        if ((e = hipGetLastError()) != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "ddf: launch of the fold: %s", hipGetErrorString(e));
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "ddf: fold: %s", hipGetErrorString(e));
+        LAUNCHED("ddf: launch of the fold");
+        HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "ddf: fold");
         return 0;
     }
     // host arrays: 0-3 the candidate's doubles, 4 its err, 5-8 the best's doubles, 9 index, 10 the best's err
-    Scratch S;
+    DeviceMem S;
     const void* src[11] = {f, T, dx, dy, err, best_f, best_T, best_dx, best_dy, index, best_err};
     void* dst[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, best_f, best_T, best_dx, best_dy, index, best_err};
     for (int q = 0; q < 11; q++) {
         const size_t bytes = n * ((q == 4 || q >= 9) ? 4 : 8);
-        if ((e = hipMalloc(&S.p[q], bytes)) != hipSuccess) { S.p[q] = nullptr; return fail(UMPA_HIP_E_NOMEM, "ddf: device memory for the fold: %s", hipGetErrorString(e)); }
+        HIPOK(S.alloc(q, bytes), UMPA_HIP_E_NOMEM, "ddf: device memory for the fold");
         if (q < 5 || (m > 0 && q < 10))                        // candidate 0 initialises the best planes: nothing of them is read
-            if ((e = hipMemcpy(S.p[q], src[q], bytes, hipMemcpyHostToDevice)) != hipSuccess)
-                return fail(UMPA_HIP_E_DEVICE, "ddf: upload of the fold's planes: %s", hipGetErrorString(e));
+            HIPOK(hipMemcpy(S.p[q], src[q], bytes, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "ddf: upload of the fold's planes");
     }
     hipLaunchKernelGGL(ddf_fold_kernel, grid, block, 0, nullptr, m, n, (const double*)S.p[0], (const double*)S.p[1], (const double*)S.p[2],
                        (const double*)S.p[3], (const int*)S.p[4], (double*)S.p[5], (double*)S.p[6], (double*)S.p[7], (double*)S.p[8],
                        (int*)S.p[9], (int*)S.p[10]);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "ddf: launch of the fold: %s", hipGetErrorString(e));
+    LAUNCHED("ddf: launch of the fold");
     for (int q = 5; q < 11; q++)
-        if ((e = hipMemcpy(dst[q], S.p[q], n * (q >= 9 ? 4 : 8), hipMemcpyDeviceToHost)) != hipSuccess)
-            return fail(UMPA_HIP_E_LAUNCH, "ddf: fold: %s", hipGetErrorString(e));
+        HIPOK(hipMemcpy(dst[q], S.p[q], n * (q >= 9 ? 4 : 8), hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "ddf: fold");
     return 0;
 }

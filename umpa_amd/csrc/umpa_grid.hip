@@ -5,12 +5,10 @@
 // umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
 #include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdarg>
 #include <cstring>
-#include <string>
 
 #include "../../include/umpa_grid.h"
+#include "umpa_host.h"
 #include "umpa_hipx.h"
 #include "umpa_grid_kernels.h"
 
@@ -19,19 +17,6 @@ using namespace umpa;
 #define UMPA_GRID_API extern "C" __attribute__((visibility("default")))
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
 
 struct GridJob {
     bool volume = false;              // cost_volume_kernel instead of grid_min_kernel

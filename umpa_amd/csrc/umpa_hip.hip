@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "../../include/umpa_hip.h"
+#include "umpa_host.h"              // g_err, fail
 #include "umpa_walk.h"
 #include "umpa_direct.h"
 #include "umpa_tiled.h"
@@ -26,19 +27,6 @@
 using namespace umpa;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
 
 #define HIP_TRY(expr, code)                                                              \
     do {                                                                                 \

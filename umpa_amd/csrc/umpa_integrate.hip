@@ -24,13 +24,11 @@
 // No CPU fallback.
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdio>
-#include <cstdarg>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "../../include/umpa_integrate.h"
+#include "umpa_host.h"
 
 #pragma clang fp contract(off)
 
@@ -506,19 +504,6 @@ using namespace umpa;
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 struct Level { int H, W; double *w, *d, *x, *t, *b; };
 
 inline dim3 blocks(int n) { return dim3((unsigned)((n + 255) / 256)); }
@@ -659,20 +644,7 @@ int check_common(int H, int W, int device, int flags, int allowed)
     return 0;
 }
 
-int check_device(int device)
-{
-    const int ndev = umpa_hip_device_count();
-    if (ndev < 1) return fail(UMPA_HIP_E_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(UMPA_HIP_E_ARG, "device %d out of range (%d devices)", device, ndev);
-    const hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "integrate: hipSetDevice(%d): %s", device, hipGetErrorString(e));
-    return 0;
-}
-
 constexpr int ALL_FLAGS = UMPA_HIP_F_DEVICE_IO | UMPA_INTEGRATE_F_NO_TAIL | UMPA_INTEGRATE_F_JACOBI | UMPA_INTEGRATE_F_DEBUG;
-
-#define LAUNCHED(what) do { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "integrate: %s: %s", what, hipGetErrorString(e_)); } while (0)
-#define HIPOK(call, code, what) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return fail(code, "integrate: %s: %s", what, hipGetErrorString(e_)); } while (0)
 
 } // namespace
 
@@ -684,35 +656,35 @@ UMPA_INTEGRATE_API int umpa_integrate_vcycle(const double* w, const double* r, d
     if (int rc = check_common(H, W, device, flags, ALL_FLAGS)) return rc;
     const bool dev_io = flags & UMPA_HIP_F_DEVICE_IO, jacobi = flags & UMPA_INTEGRATE_F_JACOBI;
     const int n = H * W;
-    if (w && !dev_io)
-        for (int i = 0; i < n; i++)
-            if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
-                return fail(UMPA_HIP_E_ARG, "integrate: weights must be finite and >= 0 (pixel (%d, %d))", i / W, i % W);
-    if (int rc = check_device(device)) return rc;
+    if (w && !dev_io) {
+        const size_t i = bad_weight(w, (size_t)n);
+        if (i < (size_t)n) return fail(UMPA_HIP_E_ARG, "integrate: weights must be finite and >= 0 (pixel (%d, %d))", (int)(i / W), (int)(i % W));
+    }
+    if (int rc = pick_device("integrate", device)) return rc;
     hipStream_t s = dev_io ? (hipStream_t)stream : nullptr;
     const auto shapes = level_shapes(H, W, jacobi);
     Slab slab;
     slab.size = hierarchy_doubles(shapes) * sizeof(double) + (dev_io ? 0 : 3 * Slab::pad(n));
-    HIPOK(hipMalloc((void**)&slab.base, slab.size), UMPA_HIP_E_NOMEM, "device memory for the workspace");
+    HIPOK(hipMalloc((void**)&slab.base, slab.size), UMPA_HIP_E_NOMEM, "integrate: device memory for the workspace");
     Hierarchy h;
     carve(h, shapes, slab, flags & UMPA_INTEGRATE_F_NO_TAIL);
     const double *dw = w, *dr = r;
     double* dz = z;
     if (!dev_io) {
         double* hw = slab.take(n); double* hr = slab.take(n); dz = slab.take(n);
-        if (w) HIPOK(hipMemcpy(hw, w, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "upload");
-        HIPOK(hipMemcpy(hr, r, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "upload");
+        if (w) HIPOK(hipMemcpy(hw, w, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "integrate: upload");
+        HIPOK(hipMemcpy(hr, r, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "integrate: upload");
         dw = w ? hw : nullptr; dr = hr;
     }
     hipLaunchKernelGGL(integrate_weights_kernel, blocks(n), dim3(256), 0, s, dw, (const double*)nullptr, (const double*)nullptr, h.lv[0].w, n);
-    LAUNCHED("weights");
-    HIPOK(build_levels(h, s), UMPA_HIP_E_LAUNCH, "building the levels");
+    LAUNCHED("integrate: weights");
+    HIPOK(build_levels(h, s), UMPA_HIP_E_LAUNCH, "integrate: building the levels");
     if (flags & UMPA_INTEGRATE_F_DEBUG)
-        HIPOK(hipMemcpyAsync(dz, h.lv[0].d, (size_t)n * 8, hipMemcpyDeviceToDevice, s), UMPA_HIP_E_LAUNCH, "copy of d");
+        HIPOK(hipMemcpyAsync(dz, h.lv[0].d, (size_t)n * 8, hipMemcpyDeviceToDevice, s), UMPA_HIP_E_LAUNCH, "integrate: copy of d");
     else
-        HIPOK(precondition(h, jacobi, dr, dz, nullptr, s), UMPA_HIP_E_LAUNCH, "the V-cycle");
-    HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "the V-cycle");
-    if (!dev_io) HIPOK(hipMemcpy(z, dz, (size_t)n * 8, hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "download");
+        HIPOK(precondition(h, jacobi, dr, dz, nullptr, s), UMPA_HIP_E_LAUNCH, "integrate: the V-cycle");
+    HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "integrate: the V-cycle");
+    if (!dev_io) HIPOK(hipMemcpy(z, dz, (size_t)n * 8, hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "integrate: download");
     return 0;
 }
 
@@ -727,11 +699,11 @@ UMPA_INTEGRATE_API int umpa_integrate_solve(const double* gx, const double* gy, 
     if (maxiter < 0) return fail(UMPA_HIP_E_ARG, "integrate: maxiter = %d", maxiter);
     const bool dev_io = flags & UMPA_HIP_F_DEVICE_IO, jacobi = flags & UMPA_INTEGRATE_F_JACOBI, debug = flags & UMPA_INTEGRATE_F_DEBUG;
     const int n = H * W;
-    if (w && !dev_io)
-        for (size_t i = 0; i < (size_t)n * K; i++)
-            if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
-                return fail(UMPA_HIP_E_ARG, "integrate: weights must be finite and >= 0 (map %d, pixel (%d, %d))", (int)(i / n), (int)(i % n / W), (int)(i % W));
-    if (int rc = check_device(device)) return rc;
+    if (w && !dev_io) {
+        const size_t i = bad_weight(w, (size_t)n * K);
+        if (i < (size_t)n * K) return fail(UMPA_HIP_E_ARG, "integrate: weights must be finite and >= 0 (map %d, pixel (%d, %d))", (int)(i / n), (int)(i % n / W), (int)(i % W));
+    }
+    if (int rc = pick_device("integrate", device)) return rc;
     if (K == 0) return 0;
     hipStream_t s = dev_io ? (hipStream_t)stream : nullptr;
 
@@ -740,7 +712,7 @@ UMPA_INTEGRATE_API int umpa_integrate_solve(const double* gx, const double* gy, 
     Slab slab;
     // x, r, z, p, Ap, b; two arrays of partial sums; the state; host arrays: gx, gy, w, phi
     slab.size = hierarchy_doubles(shapes) * sizeof(double) + 6 * Slab::pad(n) + 2 * Slab::pad(nb) + Slab::pad(32) + (dev_io ? 0 : 4 * Slab::pad(n));
-    HIPOK(hipMalloc((void**)&slab.base, slab.size), UMPA_HIP_E_NOMEM, "device memory for the workspace");
+    HIPOK(hipMalloc((void**)&slab.base, slab.size), UMPA_HIP_E_NOMEM, "integrate: device memory for the workspace");
     Hierarchy h;
     carve(h, shapes, slab, flags & UMPA_INTEGRATE_F_NO_TAIL);
     double *x = slab.take(n), *r = slab.take(n), *z = slab.take(n), *p = slab.take(n), *Ap = slab.take(n), *b = slab.take(n);
@@ -757,34 +729,34 @@ UMPA_INTEGRATE_API int umpa_integrate_solve(const double* gx, const double* gy, 
         const double *dgx = gx + (size_t)k * n, *dgy = gy + (size_t)k * n, *dw = w ? w + (size_t)k * n : nullptr;
         double* dphi = phi + (size_t)k * n;
         if (!dev_io) {
-            HIPOK(hipMemcpy(hgx, dgx, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "upload");
-            HIPOK(hipMemcpy(hgy, dgy, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "upload");
-            if (w) HIPOK(hipMemcpy(hw, dw, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "upload");
+            HIPOK(hipMemcpy(hgx, dgx, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "integrate: upload");
+            HIPOK(hipMemcpy(hgy, dgy, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "integrate: upload");
+            if (w) HIPOK(hipMemcpy(hw, dw, (size_t)n * 8, hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "integrate: upload");
             dgx = hgx; dgy = hgy; dw = w ? hw : nullptr; dphi = hphi;
         }
         hipLaunchKernelGGL(integrate_weights_kernel, grid, tb, 0, s, dw, dgx, dgy, f.w, n);
-        LAUNCHED("weights");
-        HIPOK(build_levels(h, s), UMPA_HIP_E_LAUNCH, "building the levels");
+        LAUNCHED("integrate: weights");
+        HIPOK(build_levels(h, s), UMPA_HIP_E_LAUNCH, "integrate: building the levels");
         hipLaunchKernelGGL(integrate_rhs_kernel, grid, tb, 0, s, (const double*)f.w, dgx, dgy, b, H, W);
-        LAUNCHED("rhs");
+        LAUNCHED("integrate: rhs");
         State host;
         memset(&host, 0, sizeof(host));
         host.status = UMPA_INTEGRATE_MAXITER;
         if (debug) {
-            HIPOK(hipMemcpyAsync(dphi, b, (size_t)n * 8, hipMemcpyDeviceToDevice, s), UMPA_HIP_E_LAUNCH, "copy of b");
-            HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "rhs");
+            HIPOK(hipMemcpyAsync(dphi, b, (size_t)n * 8, hipMemcpyDeviceToDevice, s), UMPA_HIP_E_LAUNCH, "integrate: copy of b");
+            HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "integrate: rhs");
         } else {
-            HIPOK(hipMemsetAsync(st, 0, sizeof(State), s), UMPA_HIP_E_LAUNCH, "state");
-            HIPOK(hipMemsetAsync(x, 0, (size_t)n * 8, s), UMPA_HIP_E_LAUNCH, "x = 0");
-            HIPOK(hipMemsetAsync(p, 0, (size_t)n * 8, s), UMPA_HIP_E_LAUNCH, "p = 0");
-            HIPOK(hipMemcpyAsync(r, b, (size_t)n * 8, hipMemcpyDeviceToDevice, s), UMPA_HIP_E_LAUNCH, "r = b");
+            HIPOK(hipMemsetAsync(st, 0, sizeof(State), s), UMPA_HIP_E_LAUNCH, "integrate: state");
+            HIPOK(hipMemsetAsync(x, 0, (size_t)n * 8, s), UMPA_HIP_E_LAUNCH, "integrate: x = 0");
+            HIPOK(hipMemsetAsync(p, 0, (size_t)n * 8, s), UMPA_HIP_E_LAUNCH, "integrate: p = 0");
+            HIPOK(hipMemcpyAsync(r, b, (size_t)n * 8, hipMemcpyDeviceToDevice, s), UMPA_HIP_E_LAUNCH, "integrate: r = b");
             hipLaunchKernelGGL(integrate_dot_kernel, grid, tb, 0, s, (const double*)b, (const double*)b, part, n, (const State*)nullptr);
             hipLaunchKernelGGL(integrate_scalar_kernel, one, tb, 0, s, (const double*)part, none, nb, st, (int)S_BNORM, tol);
-            HIPOK(precondition(h, jacobi, r, z, st, s), UMPA_HIP_E_LAUNCH, "the V-cycle");
+            HIPOK(precondition(h, jacobi, r, z, st, s), UMPA_HIP_E_LAUNCH, "integrate: the V-cycle");
             hipLaunchKernelGGL(integrate_dot_kernel, grid, tb, 0, s, (const double*)r, (const double*)z, part, n, (const State*)st);
             hipLaunchKernelGGL(integrate_scalar_kernel, one, tb, 0, s, (const double*)part, none, nb, st, (int)S_RZ0, tol);
             hipLaunchKernelGGL(integrate_direction_kernel, grid, tb, 0, s, (const double*)z, p, n, (const State*)st);   // beta = 0 and p = 0: p = z
-            LAUNCHED("the start of the iteration");
+            LAUNCHED("integrate: the start of the iteration");
             for (int it = 0; it < maxiter; it++) {
                 hipLaunchKernelGGL(integrate_apply_dot_kernel, grid, tb, 0, s, (const double*)f.w, (const double*)p, Ap, part, H, W, (const State*)st);
                 hipLaunchKernelGGL(integrate_scalar_kernel, one, tb, 0, s, (const double*)part, none, nb, st, (int)S_ALPHA, tol);
@@ -792,14 +764,14 @@ UMPA_INTEGRATE_API int umpa_integrate_solve(const double* gx, const double* gy, 
                 hipLaunchKernelGGL(integrate_scalar_kernel, one, tb, 0, s, (const double*)part, none, nb, st, (int)S_CHECK, tol);
                 hipLaunchKernelGGL(integrate_residual_kernel, grid, tb, 0, s, (const double*)f.w, (const double*)x, (const double*)b, r, part, H, W, (const State*)st, 0);
                 hipLaunchKernelGGL(integrate_scalar_kernel, one, tb, 0, s, (const double*)part, none, nb, st, (int)S_VERIFY, tol);
-                HIPOK(precondition(h, jacobi, r, z, st, s), UMPA_HIP_E_LAUNCH, "the V-cycle");
+                HIPOK(precondition(h, jacobi, r, z, st, s), UMPA_HIP_E_LAUNCH, "integrate: the V-cycle");
                 hipLaunchKernelGGL(integrate_dot_kernel, grid, tb, 0, s, (const double*)r, (const double*)z, part, n, (const State*)st);
                 hipLaunchKernelGGL(integrate_scalar_kernel, one, tb, 0, s, (const double*)part, none, nb, st, (int)S_BETA, tol);
                 hipLaunchKernelGGL(integrate_direction_kernel, grid, tb, 0, s, (const double*)z, p, n, (const State*)st);
-                LAUNCHED("an iteration");
+                LAUNCHED("integrate: an iteration");
                 if ((it + 1) % UMPA_INTEGRATE_CHECK_EVERY == 0 && it + 1 < maxiter) {
-                    HIPOK(hipMemcpyAsync(&host, st, sizeof(State), hipMemcpyDeviceToHost, s), UMPA_HIP_E_LAUNCH, "reading the flags");
-                    HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "an iteration");
+                    HIPOK(hipMemcpyAsync(&host, st, sizeof(State), hipMemcpyDeviceToHost, s), UMPA_HIP_E_LAUNCH, "integrate: reading the flags");
+                    HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "integrate: an iteration");
                     if (host.done) break;
                 }
             }
@@ -808,12 +780,12 @@ UMPA_INTEGRATE_API int umpa_integrate_solve(const double* gx, const double* gy, 
             hipLaunchKernelGGL(integrate_gauge_kernel, grid, tb, 0, s, (const double*)x, (const double*)f.d, part, part2, n);
             hipLaunchKernelGGL(integrate_scalar_kernel, one, tb, 0, s, (const double*)part, (const double*)part2, nb, st, (int)S_MEAN, tol);
             hipLaunchKernelGGL(integrate_output_kernel, grid, tb, 0, s, (const double*)x, (const double*)f.d, dphi, fill, n, (const State*)st);
-            LAUNCHED("the output");
-            HIPOK(hipMemcpyAsync(&host, st, sizeof(State), hipMemcpyDeviceToHost, s), UMPA_HIP_E_LAUNCH, "reading the state");
-            HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "the solve");
+            LAUNCHED("integrate: the output");
+            HIPOK(hipMemcpyAsync(&host, st, sizeof(State), hipMemcpyDeviceToHost, s), UMPA_HIP_E_LAUNCH, "integrate: reading the state");
+            HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "integrate: the solve");
         }
         iters[k] = host.iters; resid[k] = host.resid; status[k] = host.status;
-        if (!dev_io) HIPOK(hipMemcpy(phi + (size_t)k * n, hphi, (size_t)n * 8, hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "download");
+        if (!dev_io) HIPOK(hipMemcpy(phi + (size_t)k * n, hphi, (size_t)n * 8, hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "integrate: download");
     }
     return 0;
 }

@@ -10,12 +10,10 @@
 // No CPU fallback.
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdio>
-#include <cstdarg>
 #include <cstring>
-#include <string>
 
 #include "../../include/umpa_register.h"
+#include "umpa_host.h"
 
 #pragma clang fp contract(off)
 
@@ -211,19 +209,6 @@ using namespace umpa;
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 constexpr size_t LDS_BUDGET = 64 * 1024;
 
 size_t lds_bytes(const RegGeom& g, bool weighted, bool overlap)
@@ -274,11 +259,6 @@ void launch_norm(const void* f, unsigned n, double* out, hipStream_t s)
 {
     hipLaunchKernelGGL((register_norm_kernel<T>), dim3(NORM_BLOCKS), dim3(256), 0, s, (const T*)f, n, out);
 }
-
-struct Scratch {                       // device memory of one call
-    void* p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Scratch() { for (void* q : p) if (q) (void)hipFree(q); }
-};
 
 // One pair, every pointer a device pointer.  part: nslots * np * NS doubles; norms: 2 * NORM_BLOCKS doubles (a, then b).
 hipError_t run_pair(const void* a, const void* b, const double* w, int dtype, const RegGeom& g, bool overlap, size_t lds,
@@ -332,62 +312,51 @@ UMPA_REGISTER_API int umpa_register_sums(const void* a, const void* b, const dou
     const bool overlap = boundary == UMPA_REGISTER_OVERLAP;
     const size_t n = (size_t)H * W;
     if (w && !dev_io) {
-        const size_t nw = shared_w ? n : n * (size_t)K;
-        for (size_t i = 0; i < nw; i++)
-            if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
-                return fail(UMPA_HIP_E_ARG, "register: weights must be finite and >= 0 (plane %d, pixel (%d, %d))", (int)(i / n), (int)(i % n / W), (int)(i % W));
+        const size_t nw = shared_w ? n : n * (size_t)K, i = bad_weight(w, nw);
+        if (i < nw)
+            return fail(UMPA_HIP_E_ARG, "register: weights must be finite and >= 0 (plane %d, pixel (%d, %d))", (int)(i / n), (int)(i % n / W), (int)(i % W));
     }
     RegGeom g;
     if (!geometry(H, W, S0, S1, w != nullptr, overlap, g))
         return fail(UMPA_HIP_E_UNSUPPORTED, "register: no tile of a box of (%d, %d) fits the LDS", S0, S1);
     const size_t lds = lds_bytes(g, w != nullptr, overlap);
-    const int ndev = umpa_hip_device_count();
-    if (ndev < 1) return fail(UMPA_HIP_E_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(UMPA_HIP_E_ARG, "device %d out of range (%d devices)", device, ndev);
+    if (int rc = pick_device("register", device)) return rc;
     if (K == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "register: hipSetDevice(%d): %s", device, hipGetErrorString(e));
 
     const bool full = w || overlap;
     const int np = full ? 3 : 1, NS = g.U0 * g.U1, nslots = g.ntx * g.nty * g.nteams;
-    const size_t esz = dtype == 0 ? 8 : dtype == 1 ? 4 : 2;
-    Scratch S;                                                 // 0 part, 1 norms, 2 a, 3 b, 4 w, 5 P Q A
-    if ((e = hipMalloc(&S.p[0], (size_t)nslots * np * NS * sizeof(double))) != hipSuccess) { S.p[0] = nullptr; return fail(UMPA_HIP_E_NOMEM, "register: device memory for the partial sums: %s", hipGetErrorString(e)); }
-    if ((e = hipMalloc(&S.p[1], 2 * NORM_BLOCKS * sizeof(double))) != hipSuccess) { S.p[1] = nullptr; return fail(UMPA_HIP_E_NOMEM, "register: device memory: %s", hipGetErrorString(e)); }
+    const size_t esz = dtype_size(dtype);
+    DeviceMem S;                                               // 0 part, 1 norms, 2 a, 3 b, 4 w, 5 P Q A
+    HIPOK(S.alloc(0, (size_t)nslots * np * NS * sizeof(double)), UMPA_HIP_E_NOMEM, "register: device memory for the partial sums");
+    HIPOK(S.alloc(1, 2 * NORM_BLOCKS * sizeof(double)), UMPA_HIP_E_NOMEM, "register: device memory");
     double* part = (double*)S.p[0];
     double* norms = (double*)S.p[1];
     const char* ca = (const char*)a;
     const char* cb = (const char*)b;
     if (dev_io) {
         hipStream_t s = (hipStream_t)stream;
-        for (int k = 0; k < K; k++) {
-            e = run_pair(shared_a ? ca : ca + (size_t)k * n * esz, cb + (size_t)k * n * esz, w ? (shared_w ? w : w + (size_t)k * n) : nullptr,
-                         dtype, g, overlap, lds, part, norms, shared_a && k > 0,
-                         P + (size_t)k * NS, Q + (size_t)k * NS, A + (size_t)k * NS, s);
-            if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "register: launch of pair %d: %s", k, hipGetErrorString(e));
-        }
-        e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "register: %s", hipGetErrorString(e));
+        for (int k = 0; k < K; k++)
+            HIPOK(run_pair(shared_a ? ca : ca + (size_t)k * n * esz, cb + (size_t)k * n * esz, w ? (shared_w ? w : w + (size_t)k * n) : nullptr,
+                           dtype, g, overlap, lds, part, norms, shared_a && k > 0,
+                           P + (size_t)k * NS, Q + (size_t)k * NS, A + (size_t)k * NS, s),
+                  UMPA_HIP_E_LAUNCH, "register: launch of pair %d", k);
+        HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "register");
         return 0;
     }
     // host arrays: device copies of one pair's arrays, pair after pair on the null stream
     const size_t bytes[4] = {n * esz, n * esz, w ? n * 8 : 0, (size_t)3 * NS * 8};
     for (int q = 0; q < 4; q++)
-        if (bytes[q] && (e = hipMalloc(&S.p[2 + q], bytes[q])) != hipSuccess) { S.p[2 + q] = nullptr; return fail(UMPA_HIP_E_NOMEM, "register: device memory for a pair: %s", hipGetErrorString(e)); }
+        if (bytes[q]) HIPOK(S.alloc(2 + q, bytes[q]), UMPA_HIP_E_NOMEM, "register: device memory for a pair");
     double* dout = (double*)S.p[5];
     for (int k = 0; k < K; k++) {
-        e = hipSuccess;
-        if (!shared_a || k == 0) e = hipMemcpy(S.p[2], shared_a ? ca : ca + (size_t)k * n * esz, bytes[0], hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(S.p[3], cb + (size_t)k * n * esz, bytes[1], hipMemcpyHostToDevice);
-        if (e == hipSuccess && w && (!shared_w || k == 0)) e = hipMemcpy(S.p[4], shared_w ? w : w + (size_t)k * n, bytes[2], hipMemcpyHostToDevice);
-        if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "register: upload of pair %d: %s", k, hipGetErrorString(e));
-        e = run_pair(S.p[2], S.p[3], (const double*)S.p[4], dtype, g, overlap, lds, part, norms, shared_a && k > 0,
-                     dout, dout + NS, dout + 2 * NS, nullptr);
-        if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "register: launch of pair %d: %s", k, hipGetErrorString(e));
-        e = hipMemcpy(P + (size_t)k * NS, dout, (size_t)NS * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(Q + (size_t)k * NS, dout + NS, (size_t)NS * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(A + (size_t)k * NS, dout + 2 * NS, (size_t)NS * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "register: pair %d: %s", k, hipGetErrorString(e));
+        if (!shared_a || k == 0) HIPOK(hipMemcpy(S.p[2], shared_a ? ca : ca + (size_t)k * n * esz, bytes[0], hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "register: upload of pair %d", k);
+        HIPOK(hipMemcpy(S.p[3], cb + (size_t)k * n * esz, bytes[1], hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "register: upload of pair %d", k);
+        if (w && (!shared_w || k == 0)) HIPOK(hipMemcpy(S.p[4], shared_w ? w : w + (size_t)k * n, bytes[2], hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "register: upload of pair %d", k);
+        HIPOK(run_pair(S.p[2], S.p[3], (const double*)S.p[4], dtype, g, overlap, lds, part, norms, shared_a && k > 0,
+                       dout, dout + NS, dout + 2 * NS, nullptr), UMPA_HIP_E_LAUNCH, "register: launch of pair %d", k);
+        HIPOK(hipMemcpy(P + (size_t)k * NS, dout, (size_t)NS * 8, hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "register: pair %d", k);
+        HIPOK(hipMemcpy(Q + (size_t)k * NS, dout + NS, (size_t)NS * 8, hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "register: pair %d", k);
+        HIPOK(hipMemcpy(A + (size_t)k * NS, dout + 2 * NS, (size_t)NS * 8, hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "register: pair %d", k);
     }
     return 0;
 }

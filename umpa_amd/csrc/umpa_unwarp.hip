@@ -9,12 +9,10 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cmath>
-#include <cstdio>
-#include <cstdarg>
 #include <cstring>
-#include <string>
 
 #include "../../include/umpa_unwarp.h"
+#include "umpa_host.h"
 #define UMPA_HIPX_STAGE_ONLY          // the stage filter alone: none of the tiled path's structs, none of its kernels
 #include "umpa_hipx.h"
 #include "umpa_walk.h"                // UMPA_GLOBAL, gp, gpw
@@ -105,19 +103,6 @@ struct umpa_unwarp_map {
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 void unref(umpa_unwarp_map* map)
 {
     if (map->refs.fetch_sub(1) != 1) return;
@@ -162,11 +147,6 @@ int stage_filter(void* user, int k, const void* staged_raw, int raw_dtype, const
     return launch(*map, staged_raw, raw_dtype, dark_k, flat_k, out_k, upload_stream) == hipSuccess ? 0 : UMPA_HIP_E_LAUNCH;
 }
 
-struct Scratch {                       // device copies of one frame's arrays for the host-array call
-    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Scratch() { for (void* q : p) if (q) (void)hipFree(q); }
-};
-
 } // namespace
 
 UMPA_UNWARP_API const char* umpa_unwarp_last_error(void) { return g_err.c_str(); }
@@ -182,13 +162,7 @@ UMPA_UNWARP_API umpa_unwarp_map* umpa_unwarp_map_create(int H, int W, const floa
             fail(UMPA_HIP_E_ARG, "unwarp: the map is not finite at pixel (%d, %d)", (int)(q / W), (int)(q % W));
             return nullptr;
         }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        fail(UMPA_HIP_E_DEVICE, "no HIP device available (this library has no CPU fallback)");
-        return nullptr;
-    }
-    if (device < 0 || device >= ndev) { fail(UMPA_HIP_E_ARG, "device %d out of range (%d devices)", device, ndev); return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { fail(UMPA_HIP_E_DEVICE, "unwarp: hipSetDevice(%d) failed", device); return nullptr; }
+    if (pick_device("unwarp", device) < 0) return nullptr;
     umpa_unwarp_map* map = new umpa_unwarp_map;
     map->H = H; map->W = W; map->interp = interp; map->device = device;
     hipError_t e = hipMalloc((void**)&map->d, 2 * n * sizeof(float));
@@ -214,31 +188,26 @@ UMPA_UNWARP_API int umpa_unwarp_frames(umpa_unwarp_map* map, const void* const* 
     if (flags & ~UMPA_HIP_F_DEVICE_IO) return fail(UMPA_HIP_E_ARG, "unwarp: frames takes UMPA_HIP_F_DEVICE_IO and no other flag");
     for (int k = 0; k < K; k++)
         if (!raw[k] || !out[k] || (dark && !dark[k]) || (flat && !flat[k])) return fail(UMPA_HIP_E_ARG, "unwarp: null frame %d", k);
-    hipError_t e = hipSetDevice(map->device);
-    if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "unwarp: hipSetDevice(%d): %s", map->device, hipGetErrorString(e));
+    HIPOK(hipSetDevice(map->device), UMPA_HIP_E_DEVICE, "unwarp: hipSetDevice(%d)", map->device);    // (the map's device: it was counted at map_create)
     if (flags & UMPA_HIP_F_DEVICE_IO) {
-        for (int k = 0; k < K; k++) {
-            e = launch(*map, raw[k], raw_dtype, dark ? dark[k] : nullptr, flat ? flat[k] : nullptr, out[k], (hipStream_t)stream);
-            if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "unwarp: launch of frame %d: %s", k, hipGetErrorString(e));
-        }
+        for (int k = 0; k < K; k++)
+            HIPOK(launch(*map, raw[k], raw_dtype, dark ? dark[k] : nullptr, flat ? flat[k] : nullptr, out[k], (hipStream_t)stream),
+                  UMPA_HIP_E_LAUNCH, "unwarp: launch of frame %d", k);
         return 0;
     }
     // host arrays: device copies of one frame's arrays, frame after frame on the null stream (a call made once per
     // calibration set, not the streaming path: that is umpa_unwarp_attach)
-    const size_t n = (size_t)map->H * map->W, esz = raw_dtype == 0 ? 8 : raw_dtype == 1 ? 4 : 2;
-    Scratch S;
+    const size_t n = (size_t)map->H * map->W, esz = dtype_size(raw_dtype);
+    DeviceMem S;
     const size_t bytes[4] = {n * esz, n * 8, dark ? n * 8 : 0, flat ? n * 8 : 0};      // raw, out, dark, flat
     for (int q = 0; q < 4; q++)
-        if (bytes[q] && (e = hipMalloc(&S.p[q], bytes[q])) != hipSuccess) { S.p[q] = nullptr; return fail(UMPA_HIP_E_NOMEM, "unwarp: device memory for a frame: %s", hipGetErrorString(e)); }
+        if (bytes[q]) HIPOK(S.alloc(q, bytes[q]), UMPA_HIP_E_NOMEM, "unwarp: device memory for a frame");
     for (int k = 0; k < K; k++) {
-        e = hipMemcpy(S.p[0], raw[k], bytes[0], hipMemcpyHostToDevice);
-        if (e == hipSuccess && dark) e = hipMemcpy(S.p[2], dark[k], bytes[2], hipMemcpyHostToDevice);
-        if (e == hipSuccess && flat) e = hipMemcpy(S.p[3], flat[k], bytes[3], hipMemcpyHostToDevice);
-        if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "unwarp: upload of frame %d: %s", k, hipGetErrorString(e));
-        e = launch(*map, S.p[0], raw_dtype, (const double*)S.p[2], (const double*)S.p[3], (double*)S.p[1], nullptr);
-        if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "unwarp: launch of frame %d: %s", k, hipGetErrorString(e));
-        e = hipMemcpy(out[k], S.p[1], bytes[1], hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "unwarp: frame %d: %s", k, hipGetErrorString(e));
+        HIPOK(hipMemcpy(S.p[0], raw[k], bytes[0], hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "unwarp: upload of frame %d", k);
+        if (dark) HIPOK(hipMemcpy(S.p[2], dark[k], bytes[2], hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "unwarp: upload of frame %d", k);
+        if (flat) HIPOK(hipMemcpy(S.p[3], flat[k], bytes[3], hipMemcpyHostToDevice), UMPA_HIP_E_DEVICE, "unwarp: upload of frame %d", k);
+        HIPOK(launch(*map, S.p[0], raw_dtype, (const double*)S.p[2], (const double*)S.p[3], (double*)S.p[1], nullptr), UMPA_HIP_E_LAUNCH, "unwarp: launch of frame %d", k);
+        HIPOK(hipMemcpy(out[k], S.p[1], bytes[1], hipMemcpyDeviceToHost), UMPA_HIP_E_LAUNCH, "unwarp: frame %d", k);
     }
     return 0;
 }

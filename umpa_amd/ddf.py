@@ -159,17 +159,13 @@ def blur_frames(frames, abc, device=None):
         raise ValueError("frames of %d x %d pixels are smaller than the %d x %d kernel" % (sh[0], sh[1], TAPS, TAPS))
     if on_device:
         import torch
-        d = flist[0].device
-        dev = d.index if d.index is not None else torch.cuda.current_device()
-        out = torch.empty((len(flist),) + sh, dtype=torch.float64, device=d)
-        _blur_device(flist, [out[k] for k in range(len(flist))], g, dev, torch.cuda.current_stream(d).cuda_stream)
+        dev, stream = _lib.device_io(*flist)
+        out = torch.empty((len(flist),) + sh, dtype=torch.float64, device=flist[0].device)
+        _blur_device(flist, [out[k] for k in range(len(flist))], g, dev, stream)
     else:
-        if device is None:
-            from . import model
-            device = model._default_device()
         out = np.empty((len(flist),) + sh, dtype=np.float64)
         rc = lib.blur(_table([f.ctypes.data for f in flist]), _table([out[k].ctypes.data for k in range(len(flist))]),
-                      len(flist), sh[0], sh[1], g.ctypes.data_as(_vp), int(device), 0, None)
+                      len(flist), sh[0], sh[1], g.ctypes.data_as(_vp), _lib.host_device(device), 0, None)
         lib.check(rc, "ddf blur")
     return out[0] if single else out
 
@@ -182,10 +178,7 @@ def fold(m, cand, best, device=None):
     for x, dt in list(zip(cand, [np.float64] * 4 + [np.int32])) + list(zip(best, [np.float64] * 4 + [np.int32] * 2)):
         if x.dtype != dt or not x.flags.c_contiguous or x.size != n:
             raise ValueError("fold planes must be C-contiguous float64 (int32: err, index) arrays of one size")
-    if device is None:
-        from . import model
-        device = model._default_device()
-    rc = lib.fold(int(m), n, *[x.ctypes.data_as(_vp) for x in cand], *[x.ctypes.data_as(_vp) for x in best], int(device), 0, None)
+    rc = lib.fold(int(m), n, *[x.ctypes.data_as(_vp) for x in cand], *[x.ctypes.data_as(_vp) for x in best], _lib.host_device(device), 0, None)
     lib.check(rc, "ddf fold")
 
 
@@ -229,7 +222,7 @@ class KernelSearch:
         self._lib = _lib.ddf()
         if hasattr(sam_list[0], "data_ptr") and device is None:
             device = sam_list[0].device.index
-        self._device = model._default_device() if device is None else int(device)
+        self._device = _lib.host_device(device)
         if _lib.hip().device_count() < 1:
             raise _lib.NativeError("no HIP device available (this library has no CPU fallback)")
         self._tdev = torch.device("cuda", self._device)

@@ -66,16 +66,12 @@ def _is_device(*arrays):
 
 def _check_tensors(*tensors):
     import torch
-    first = tensors[0]
     for t in tensors:
         if t is None:
             continue
         if t.dtype != torch.float64:
             raise ValueError("gradients and weights must be float64, not %s" % t.dtype)
-        if not t.is_contiguous() or not t.is_cuda or t.device != first.device:
-            raise ValueError("device arrays must be contiguous HIP tensors on one device")
-    dev = first.device.index if first.device.index is not None else torch.cuda.current_device()
-    return dev, torch.cuda.current_stream(first.device).cuda_stream
+    return _lib.device_io(*tensors)
 
 
 def _solve(gx, gy, weight, tol, maxiter, fill, device, flags):
@@ -101,15 +97,12 @@ def _solve(gx, gy, weight, tol, maxiter, fill, device, flags):
         _check_shapes(gx.shape, gy.shape, None if weight is None else weight.shape)
         if weight is not None and not (np.isfinite(weight).all() and (weight >= 0).all()):
             raise ValueError("weights must be finite and >= 0")
-        if device is None:
-            from . import model
-            device = model._default_device()
         K = gx.shape[0] if gx.ndim == 3 else 1
         phi = np.empty_like(gx)
         it, st, res = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32), np.zeros(K)
         rc = lib.solve(gx.ctypes.data_as(vp), gy.ctypes.data_as(vp), weight.ctypes.data_as(vp) if weight is not None else None,
                        K, gx.shape[-2], gx.shape[-1], float(tol), int(maxiter), float(fill), phi.ctypes.data_as(vp),
-                       it.ctypes.data_as(vp), res.ctypes.data_as(vp), st.ctypes.data_as(vp), int(device), flags, None)
+                       it.ctypes.data_as(vp), res.ctypes.data_as(vp), st.ctypes.data_as(vp), _lib.host_device(device), flags, None)
         lib.check(rc, "integrate solve")
         single = gx.ndim == 2
     if single:
@@ -164,13 +157,10 @@ def vcycle(r, weight=None, device=None, no_tail=False, jacobi=False, diagonal=Fa
         raise ValueError("r must be [H, W] and weight of the same shape")
     if weight is not None and not (np.isfinite(weight).all() and (weight >= 0).all()):
         raise ValueError("weights must be finite and >= 0")
-    if device is None:
-        from . import model
-        device = model._default_device()
     z = np.empty_like(r)
     vp = C.c_void_p
     rc = lib.vcycle(weight.ctypes.data_as(vp) if weight is not None else None, r.ctypes.data_as(vp), z.ctypes.data_as(vp),
-                    r.shape[0], r.shape[1], int(device), flags, None)
+                    r.shape[0], r.shape[1], _lib.host_device(device), flags, None)
     lib.check(rc, "integrate vcycle")
     return z
 

@@ -73,14 +73,10 @@ def shift_sums(a, b, w=None, max_shift=8, boundary="wrap", device=None):
         if code is None or a.dtype != b.dtype or (w is not None and w.dtype != torch.float64):
             raise ValueError("frames must be float64, float32 or uint16 (a and b alike), weights float64.")
         _check_shapes(a.shape, b.shape, None if w is None else w.shape, S)
-        for t in (a, b, w):
-            if t is not None and (not t.is_contiguous() or t.device != b.device or not t.is_cuda):
-                raise ValueError("device arrays must be contiguous HIP tensors on one device")
+        dev, stream = _lib.device_io(b, a, w)
         K = b.shape[0] if b.dim() == 3 else 1
         out = torch.empty((3, K) + U, dtype=torch.float64, device=b.device)
         flags = _lib.F_DEVICE_IO | (_lib.REGISTER_F_SHARED_A if a.dim() == 2 else 0) | (_lib.REGISTER_F_SHARED_W if w is not None and w.dim() == 2 else 0)
-        dev = b.device.index if b.device.index is not None else torch.cuda.current_device()
-        stream = torch.cuda.current_stream(b.device).cuda_stream
         rc = lib.sums(a.data_ptr(), b.data_ptr(), w.data_ptr() if w is not None else None, code, K, b.shape[-2], b.shape[-1],
                       S[0], S[1], BOUNDARY[boundary], out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), dev, flags, stream)
         lib.check(rc, "register sums")
@@ -98,13 +94,10 @@ def shift_sums(a, b, w=None, max_shift=8, boundary="wrap", device=None):
     K = b.shape[0] if b.ndim == 3 else 1
     out = np.empty((3, K) + U, dtype=np.float64)
     flags = (_lib.REGISTER_F_SHARED_A if a.ndim == 2 else 0) | (_lib.REGISTER_F_SHARED_W if w is not None and w.ndim == 2 else 0)
-    if device is None:
-        from . import model
-        device = model._default_device()
     vp = C.c_void_p
     rc = lib.sums(a.ctypes.data_as(vp), b.ctypes.data_as(vp), w.ctypes.data_as(vp) if w is not None else None, code, K,
                   b.shape[-2], b.shape[-1], S[0], S[1], BOUNDARY[boundary],
-                  out[0].ctypes.data_as(vp), out[1].ctypes.data_as(vp), out[2].ctypes.data_as(vp), int(device), flags, None)
+                  out[0].ctypes.data_as(vp), out[1].ctypes.data_as(vp), out[2].ctypes.data_as(vp), _lib.host_device(device), flags, None)
     lib.check(rc, "register sums")
     return tuple(out[i] if b.ndim == 3 else out[i, 0] for i in range(3))
 
