@@ -13,6 +13,8 @@ callers of ``UMPA/align.py`` that wrap the match (``UMPA_normal``, ``UMPA_nobias
 weighted least-squares integration on ``libumpa_integrate.so``.
 ``KernelSearch`` (``umpa_amd.ddf``) finds the blur kernel ``(a, b, c)`` of the kernel dark-field model among candidates, per
 pixel, on ``libumpa_ddf.so``: the directional dark-field signal.
+``match_smooth`` / ``aggregate`` (``umpa_amd.smooth``) regularise the integer shift field by path aggregation over the cost
+volume on ``libumpa_smooth.so`` and start the ordinary walk from it.
 """
 from . import model
 from . import align
@@ -23,7 +25,10 @@ from .unwarp import UnwarpMap
 from .integrate import integrate, vcycle, phase_from_match, Integration
 from . import ddf
 from .ddf import (KernelSearch, gaussian_kernel, kernel_from_sigma, sigma_from_kernel, candidate_grid, blur_frames)
+from . import smooth
+from .smooth import aggregate, cost_scale, match_smooth
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
            "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration",
-           "ddf", "KernelSearch", "gaussian_kernel", "kernel_from_sigma", "sigma_from_kernel", "candidate_grid", "blur_frames"]
+           "ddf", "KernelSearch", "gaussian_kernel", "kernel_from_sigma", "sigma_from_kernel", "candidate_grid", "blur_frames",
+           "smooth", "aggregate", "cost_scale", "match_smooth"]

@@ -208,6 +208,16 @@ _DDF_ABI = {
 }
 DDF_SYMBOLS = list(_DDF_ABI)
 
+# include/umpa_smooth.h: path aggregation over a cost volume and the per-pixel selection
+SMOOTH_LIB_PATH = os.path.join(_HERE, "libumpa_smooth.so")
+SMOOTH_MIN_U, SMOOTH_MAX_U, SMOOTH_ALL_DIRS = 3, 15, 0xFF
+_SMOOTH_ABI = {
+    "aggregate": (_int, [_vp] + [_int] * 3 + [_dbl] * 2 + [_int] + [_vp] * 5 + [_int, _int, _vp]),
+    "workspace_bytes": (C.c_longlong, [_int] * 4),
+    "last_error": (C.c_char_p, []),
+}
+SMOOTH_SYMBOLS = list(_SMOOTH_ABI)
+
 
 def grid():
     return _satellite("grid", _GRID_ABI)
@@ -227,6 +237,10 @@ def integrate():
 
 def ddf():
     return _satellite("ddf", _DDF_ABI)
+
+
+def smooth():
+    return _satellite("smooth", _SMOOTH_ABI)
 
 
 def device_io(*tensors):
