@@ -15,6 +15,8 @@ weighted least-squares integration on ``libumpa_integrate.so``.
 pixel, on ``libumpa_ddf.so``: the directional dark-field signal.
 ``match_smooth`` / ``aggregate`` (``umpa_amd.smooth``) regularise the integer shift field by path aggregation over the cost
 volume on ``libumpa_smooth.so`` and start the ordinary walk from it.
+``uncertainty`` (``umpa_amd.sigma``) gives the per-pixel standard deviations of ``dx``, ``dy`` and a noise estimate, on
+``libumpa_sigma.so``; ``Uncertainty.weight()`` feeds ``phase_from_match``.
 """
 from . import model
 from . import align
@@ -27,8 +29,11 @@ from . import ddf
 from .ddf import (KernelSearch, gaussian_kernel, kernel_from_sigma, sigma_from_kernel, candidate_grid, blur_frames)
 from . import smooth
 from .smooth import aggregate, cost_scale, match_smooth
+from . import sigma
+from .sigma import uncertainty, Uncertainty
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
            "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration",
            "ddf", "KernelSearch", "gaussian_kernel", "kernel_from_sigma", "sigma_from_kernel", "candidate_grid", "blur_frames",
-           "smooth", "aggregate", "cost_scale", "match_smooth"]
+           "smooth", "aggregate", "cost_scale", "match_smooth",
+           "sigma", "uncertainty", "Uncertainty"]

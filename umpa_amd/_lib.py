@@ -218,6 +218,16 @@ _SMOOTH_ABI = {
 }
 SMOOTH_SYMBOLS = list(_SMOOTH_ABI)
 
+# include/umpa_sigma.h: the covariance of a matched shift and the noise estimate from the residual
+SIGMA_LIB_PATH = os.path.join(_HERE, "libumpa_sigma.so")
+SIGMA_MAX_NW, SIGMA_PLANES, SIGMA_SKIP = 8, (16, 34), -2 ** 31
+_SIGMA_ABI = {
+    "region": (_int, [_vp, _vp] + [_int] * 3 + [_vp] + [_int] * 9 + [_vp] * 6 + [_int, _int, _vp]),
+    "solve": (_int, [_vp, _int, _int, C.c_longlong, _dbl] + [_vp] * 4 + [_int, _int, _vp]),
+    "last_error": (C.c_char_p, []),
+}
+SIGMA_SYMBOLS = list(_SIGMA_ABI)
+
 
 def grid():
     return _satellite("grid", _GRID_ABI)
@@ -241,6 +251,10 @@ def ddf():
 
 def smooth():
     return _satellite("smooth", _SMOOTH_ABI)
+
+
+def sigma():
+    return _satellite("sigma", _SIGMA_ABI)
 
 
 def device_io(*tensors):

@@ -676,6 +676,11 @@ class UMPAModelNoDF(UMPAModelBase):
         return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
     cost_volume.__doc__ = UMPAModelBase._COST_VOLUME_DOC
 
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None):
+        """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
+        from . import sigma
+        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step)
+
 
 class UMPAModelDF(UMPAModelBase):
     """Mirror of ``UMPAModelDF`` (``model.pyx:824-896``)."""
@@ -704,6 +709,11 @@ class UMPAModelDF(UMPAModelBase):
     def cost_volume(self, ROI=None, step=None, with_fit=False):
         return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
     cost_volume.__doc__ = UMPAModelBase._COST_VOLUME_DOC
+
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None):
+        """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
+        from . import sigma
+        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step)
 
     @property
     def Im(self):
@@ -750,3 +760,6 @@ class UMPAModelDFKernel(UMPAModelBase):
         result = self._match(step=step, input_values=values, dxdy=dxdy, ROI=ROI,
                              num_threads=num_threads, quiet=quiet)
         return self._unpack(result, False)
+
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None):
+        raise RuntimeError("uncertainty: the kernel dark-field model is not supported")
