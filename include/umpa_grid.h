@@ -44,7 +44,9 @@ int umpa_grid_match_region(umpa_hip_model *m, int start0, int step0, int N0, int
 
 /* cost[(si + max_shift - 1) * U + (sj + max_shift - 1)][xi][xj], U = 2 max_shift - 1, for the region's N0 x N1 pixels
  * (si: row shift, sj: column shift); `T` and `df` (dark-field model only) in the same layout, each may be NULL.
- * Host arrays, or device arrays with UMPA_HIP_F_DEVICE_IO (the call then only enqueues work on `stream`); no other flag.
+ * Host arrays, or device arrays with UMPA_HIP_F_DEVICE_IO (the call then only enqueues work on `stream`).
+ * UMPA_HIP_F_USE_STAGED: the stack uploaded by umpa_hip_stage_sample is adopted first, as by umpa_hip_match_region, and
+ * the volume is that stack's; the matches that follow read it too.  Any other flag is UMPA_HIP_E_ARG.
  * An array holds U * U * N0 * N1 doubles. */
 int umpa_grid_cost_volume(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
                           double *cost, double *T, double *df, int flags, void *stream);

@@ -61,7 +61,8 @@ extern "C" {
                                         (umpa_hip_update_frames / set_window invalidate); for borrowed device frames the caller vouches.
                                         Results are identical with and without. */
 
-#define UMPA_HIP_F_USE_STAGED      32 /* the stack uploaded by umpa_hip_stage_sample becomes the sample stack of this match */
+#define UMPA_HIP_F_USE_STAGED      32 /* the stack uploaded by umpa_hip_stage_sample becomes the sample stack of this match (of this
+                                         volume, for umpa_grid_cost_volume) and stays it; without a staged stack: UMPA_HIP_E_ARG */
 #define UMPA_HIP_F_FORCE_PLAIN_DIRECT 128 /* with F_FORCE_DIRECT: the plain direct kernel (windows through L1) even where the
                                              staged one (windows out of LDS) applies; the two give identical results */
 #define UMPA_HIP_F_ASYNC           64 /* host-array call: enqueue the kernels and the downloads (into page-locked arrays) and
@@ -91,7 +92,10 @@ umpa_hip_model *umpa_hip_create(int kind, int Na, const int *dims,
 /* Replace the contents of the resident sample and/or reference stacks (same shapes; NULL = keep).
  * No counterpart in the reference, whose models borrow host pointers (model.pyx:123-129): there a caller
  * such as umpa_multi.py:149 builds a new model per projection.  Here the reference stack can stay in HBM
- * while projections stream through. */
+ * while projections stream through.
+ * The last stack wins: with a non-NULL `sam` a stack that umpa_hip_stage_sample uploaded and no call has adopted yet is
+ * dropped (UMPA_HIP_F_USE_STAGED is then UMPA_HIP_E_ARG until the next umpa_hip_stage_sample); `ref` alone leaves a staged
+ * stack pending. */
 int umpa_hip_update_frames(umpa_hip_model *m, double *const *sam, double *const *ref);
 
 /* The step-scan pipeline of UMPA/umpa_multi.py:133-150 on one GPU: upload the NEXT projection while the current
@@ -99,8 +103,10 @@ int umpa_hip_update_frames(umpa_hip_model *m, double *const *sam, double *const 
  * detector counts; page-locked memory -- umpa_hip_host_alloc / umpa_hip_host_register -- makes the call return at
  * once), copied on the model's upload stream and written to the model's BACK sample buffer as
  * (raw - dark) / flat   (dark[k], flat[k]: device float64 frames, or NULL tables: plain conversion) -- the flat-field
- * correction of umpa_multi.py:144 fused into the upload.  The staged stack becomes the sample stack at the next
- * umpa_hip_match_region with UMPA_HIP_F_USE_STAGED, in stream order.  Only for models that own their frames. */
+ * correction of umpa_multi.py:144 fused into the upload.  The staged stack becomes the sample stack at the next call that
+ * reads the sample stack and is given UMPA_HIP_F_USE_STAGED (umpa_hip_match_region, umpa_grid_match_region,
+ * umpa_grid_cost_volume), in stream order.  A later umpa_hip_stage_sample replaces a stack not adopted yet, and so does
+ * umpa_hip_update_frames with a sample stack: the last stack wins.  Only for models that own their frames. */
 int umpa_hip_stage_sample(umpa_hip_model *m, const void *const *raw, int raw_dtype,
                           const double *const *dark, const double *const *flat);
 /* Device-resident outputs (UMPA_HIP_F_DEVICE_IO) in row pieces: the region is matched in row chunks of `piece_rows`

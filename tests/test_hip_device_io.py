@@ -1,5 +1,5 @@
 """
-The device-pointer entry points of the five side libraries between canaries (tests/guarded.py): one guarded call each.
+The device-pointer entry points of the seven side libraries between canaries (tests/guarded.py): one guarded call each.
 
 Every input array lies inside a larger tensor with guards of NaN, then of 1e300 (two rows and a wavefront long, so an overrun
 lands in the test's own memory), every output array inside one of its own; the call runs on a side stream.  The outputs must
@@ -7,9 +7,9 @@ equal those of the same call on plain tensors bit for bit -- a read of a neighbo
 it with the fill --, every guard must keep its bit pattern and every input its bits.  No tolerance appears in this file; what
 the numbers ARE is the business of each library's own test module.
 
-None of the five headers documents an alignment requirement: umpa_ddf_blur chooses its 16-byte kernel on the host from the
-addresses of ALL frames of a launch and W's parity, the others load single elements.  So the misaligned calls are made, not
-refused.
+None of the seven headers documents an alignment requirement: umpa_ddf_blur chooses its 16-byte kernel on the host from the
+addresses of ALL frames of a launch and W's parity, the others (umpa_smooth_aggregate, umpa_sigma_region and umpa_sigma_solve
+among them) load single elements.  So the misaligned calls are made, not refused.
 """
 import ctypes
 
@@ -297,3 +297,111 @@ def test_grid_search_and_cost_volume(dev, frames):
         np.testing.assert_array_equal(x, vhost[k], err_msg="volume " + k)
     if hs is not None:
         G.check(hs, "grid: the borrowed stack")
+
+
+# ----------------------------------------------------------------------------- umpa_smooth_aggregate
+
+@pytest.mark.parametrize("lean", [False, True], ids=["every_output", "shift_alone"])
+def test_smooth_aggregate(dev, lean):
+    """U = 5 on 21 x 37 pixels: off the 8 columns of the march and off the 32 x 32 tiles of the transpose in both directions,
+    all eight directions (both transposed scratch volumes are in play; they are the library's own).  Once with shift, smin,
+    margin, valid and total between guards, once with shift alone (the others null: the sum is then the library's own volume
+    too).  The volume holds NaN and +-INF entries beside the NaN guards.  Guards sized by the longer side: the horizontal
+    passes march over the transposed volume, whose rows are N0 long."""
+    import smooth_expect as SE
+    from umpa_amd import _lib
+    lib = _lib.smooth()
+    U, N0, N1, lam, trunc = 5, 21, 37, 0.5, 2.25
+    cost = SE.with_specials(SE.random_volume(U, N0, N1, 11), 12)
+    assert np.isnan(cost).any() and (cost == np.inf).any() and (cost == -np.inf).any()
+    row = max(N0, N1)
+    ptr = lambda t: None if t is None else VP(t.data_ptr())
+
+    def call(A, stream):
+        (fcost,) = A.inp([cost], row)
+        (shift,) = A.out([np.zeros((2, N0, N1), np.int32)], row)
+        smin = margin = valid = total = None
+        if not lean:
+            smin, margin = A.out([np.zeros((N0, N1))] * 2, row)
+            (valid,) = A.out([np.zeros((N0, N1), np.int32)], row)
+            (total,) = A.out([np.zeros((U, U, N0, N1))], row)
+        if A.odd:
+            assert fcost.data_ptr() % 16 == 8 and shift.data_ptr() % 8 == 4
+        lib.check(lib.aggregate(ptr(fcost), U, N0, N1, lam, trunc, 0xFF, ptr(shift), ptr(smin), ptr(margin), ptr(valid), ptr(total),
+                                dev.index, _lib.F_DEVICE_IO, stream), "smooth aggregate")
+        return [shift] if lean else [shift, smin, margin, valid, total]
+
+    got = _guarded_equals_plain(dev, call, "smooth aggregate, %s" % ("shift alone" if lean else "every output"), odd=(False, True))
+    want = SE.aggregate(cost, lam, trunc, 0xFF)
+    for g, k in zip(got, ("shift", "smin", "margin", "valid", "total")):
+        np.testing.assert_array_equal(g, want[k], err_msg=k)
+    assert want["valid"].min() == 0 and want["valid"].max() == 1
+
+
+# ----------------------------------------------------------------------------- umpa_sigma_region / umpa_sigma_solve
+
+@pytest.mark.parametrize("kind", [0, 1], ids=["plain", "dark_field"])
+def test_sigma_region_and_solve(dev, kind):
+    """the 3 x 40 x 44 stacks of tests/sigma_expect.py, Nw = 2, max_shift = 3, a region with an offset and a step whose 27 x 17
+    pixels are off the 32 x 8 of the moments kernel; the shift field holds one skipped pixel and one shift far out of range at
+    a corner.  Stacks and shift field are guarded inputs, every result a guarded output; once more with the moments null; then
+    umpa_sigma_solve on the moments of the first call, 459 pixels (off the 256 of a workgroup)."""
+    import sigma_expect as SG
+    from umpa_amd import _lib
+    lib = _lib.sigma()
+    H, W, K, Nw, ms = 40, 44, 3, 2, 3
+    reg = (1, 1, 27, 0, 2, 17)
+    N0, N1, P = reg[2], reg[5], SG.PLANES[kind]
+    sam, ref = SG.stack(H, W, K, ms, kind)
+    assert sam.shape == (K, H, W)
+    shift = SG.random_shift(N0, N1, ms, 33)
+    shift[:, 5, 7] = SG.SKIP
+    shift[:, N0 - 1, N1 - 1] = (-10 ** 6, 10 ** 6)
+    skipped = ~SG.guard(shift, ms)
+    assert skipped.sum() == 2
+    win = SG.window(Nw)
+    sv = SG.window_sv(win)
+    ptr = lambda t: None if t is None else VP(t.data_ptr())
+
+    def outputs(A, n_shape, row):
+        (unit,) = A.out([np.zeros((3,) + n_shape)], row)
+        s2, dof = A.out([np.zeros(n_shape)] * 2, row)
+        (valid,) = A.out([np.zeros(n_shape, np.int32)], row)
+        return unit, s2, dof, valid
+
+    def region(with_moments):
+        def call(A, stream):
+            fsam, fref = A.inp([sam, ref], W)
+            (fshift,) = A.inp([shift], N1)
+            moments = A.out([np.zeros((P, N0, N1))], N1)[0] if with_moments else None
+            unit, s2, dof, valid = outputs(A, (N0, N1), N1)
+            if A.odd:
+                assert fsam.data_ptr() % 16 == 8 and fshift.data_ptr() % 8 == 4
+            lib.check(lib.region(ptr(fsam), ptr(fref), K, H, W, win.ctypes.data_as(VP), Nw, ms, kind, *reg, ptr(fshift), ptr(moments),
+                                 ptr(unit), ptr(s2), ptr(dof), ptr(valid), dev.index, _lib.F_DEVICE_IO, stream), "sigma region")
+            return ([moments] if with_moments else []) + [unit, s2, dof, valid]
+        return call
+
+    what = "sigma region, kind %d" % kind
+    moments, unit, s2, dof, valid = _guarded_equals_plain(dev, region(True), what, odd=(False, True))
+    lean = _guarded_equals_plain(dev, region(False), what + ", moments null", odd=(False, True))
+    want = SG.solve(moments, kind, K, sv)
+    for g, l, k in zip((unit, s2, dof, valid), lean, ("unit", "s2", "dof", "valid")):
+        np.testing.assert_array_equal(l, g, err_msg=k + ", moments null")
+        np.testing.assert_array_equal(g, want[k], err_msg=k)
+    assert np.isnan(moments[:, skipped]).all() and np.isfinite(moments[:, ~skipped]).all()
+    assert (valid[skipped] == 0).all() and valid[~skipped].mean() > 0.5
+
+    n = N0 * N1
+    assert n == 459 and n % 256 != 0
+    flat = moments.reshape(P, n)
+
+    def solve(A, stream):
+        (fm,) = A.inp([flat], n)
+        out = outputs(A, (n,), n)
+        lib.check(lib.solve(ptr(fm), kind, K, n, sv, *[ptr(o) for o in out], dev.index, _lib.F_DEVICE_IO, stream), "sigma solve")
+        return list(out)
+
+    solved = _guarded_equals_plain(dev, solve, "sigma solve, kind %d" % kind, odd=(False, True))
+    for g, r, k in zip(solved, (unit, s2, dof, valid), ("unit", "s2", "dof", "valid")):
+        np.testing.assert_array_equal(g.reshape(r.shape), r, err_msg="solve: " + k)

@@ -396,3 +396,34 @@ def test_refusals_and_the_walk_afterwards(hip_ns):
     m.cost_volume()
     after = m.match(quiet=True)
     _same(before, after, what="walk after grid")
+
+
+def test_cost_volume_flags(hip_ns):
+    """umpa_grid_cost_volume takes UMPA_HIP_F_DEVICE_IO and UMPA_HIP_F_USE_STAGED; every other flag is refused by name before
+    anything runs, and the staged flag without a staged stack by the match entry point underneath.  (What the volume of an
+    adopted stack IS: tests/test_hip_longlived.py.)"""
+    from umpa_amd import _lib
+    sam, ref, c = GE.stack("64x72x3")
+    m = _model(hip_ns, 1, sam, ref, c["Nw"], c["ms"])
+    before = m.cost_volume()["cost"]
+    g = _lib.grid()
+    N0, N1 = m.extent
+    U = 2 * c["ms"] - 1
+    vol = np.zeros((U, U, N0, N1))
+    call = lambda flags: g.cost_volume(m._handle, 0, 1, N0, 0, 1, N1, vol.ctypes.data, None, None, flags, None)
+    for flags in (_lib.F_FORCE_DIRECT, _lib.F_FORCE_TILED, _lib.F_PLANAR, _lib.F_REUSE_REF_MAPS, _lib.F_ASYNC, _lib.F_FORCE_PLAIN_DIRECT,
+                  _lib.F_USE_STAGED | _lib.F_ASYNC, _lib.F_DEVICE_IO | _lib.F_PLANAR, 256):
+        assert call(flags) == -1, flags
+        assert g.error() == "grid: cost_volume takes UMPA_HIP_F_DEVICE_IO, UMPA_HIP_F_USE_STAGED and no other flag", (flags, g.error())
+    assert call(_lib.F_USE_STAGED) == -1 and "UMPA_HIP_F_USE_STAGED without a staged sample stack" in g.error(), g.error()
+    assert (vol == 0).all()
+    assert call(0) >= 0, g.error()                                    # the consumer was cleared, the model is as it was
+    np.testing.assert_array_equal(vol, before)
+    m.stage_sample(list(np.ascontiguousarray(1.25 * sam[::-1])))
+    assert call(_lib.F_USE_STAGED) >= 0, g.error()                    # with a staged stack the flag is taken ...
+    assert not np.array_equal(vol, before)
+    assert call(_lib.F_USE_STAGED) == -1 and "without a staged sample stack" in g.error()      # ... once
+    fresh = _model(hip_ns, 1, np.ascontiguousarray(1.25 * sam[::-1]), ref, c["Nw"], c["ms"])
+    np.testing.assert_array_equal(vol, fresh.cost_volume()["cost"])
+    m._use_staged = False                                             # (spent through the C ABI, past the Python bookkeeping)
+    np.testing.assert_array_equal(m.cost_volume()["cost"], vol)

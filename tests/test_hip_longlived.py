@@ -13,6 +13,10 @@ A trajectory here is a list of steps applied to ONE model; beside it the harness
 should now be.  After every match a fresh twin is built from that record, matched once with the same arguments under the
 same environment, and the two results must be equal bit for bit, ``last_path`` included.  No tolerance appears in this file.
 
+Every consumer of a live model is a step: ``match()`` (walk and grid search), ``cost_volume()``, ``smooth.match_smooth(model)``
+and ``model.uncertainty(result)``.  Trajectories 9 to 13 put the later three behind staged, updated and rewritten stacks: a
+staged stack is adopted by the FIRST call that reads the sample stack, whichever it is, and the last stack given wins.
+
 Each trajectory prints one line (steps compared, paths seen) for the record.
 """
 import os
@@ -64,8 +68,10 @@ class LongLived:
     masks, positions, the window_size of the constructor (padding and extent are fixed there) and the Nw set since,
     assign_coordinates, sub_pixel_mode, debug, the ROI, the forced path and the attached unwarp map."""
 
-    def __init__(self, hip_ns, cls, sam, ref, window_size, max_shift, mask=None, pos=None, force=0, label=""):
-        self.ns, self.label = hip_ns, label or cls
+    def __init__(self, hip_ns, cls, sam, ref, window_size, max_shift, mask=None, pos=None, force=0, label="", borrowed=False):
+        """borrowed: the model borrows device frames (the planes of one tensor per stack), `write` rewrites them in place, and
+        the twin is a fresh borrowed model on device copies of the record"""
+        self.ns, self.label, self.borrowed = hip_ns, label or cls, borrowed
         self.rec = dict(cls=cls, sam=("host", np.ascontiguousarray(sam)), ref=np.ascontiguousarray(ref), mask=mask, pos=pos,
                         window_size=window_size, max_shift=max_shift, Nw=None, assign="sam", subpx=-1, debug=True, ROI=None,
                         force=force, unwarp=None)
@@ -81,7 +87,10 @@ class LongLived:
         if r["pos"] is not None:
             kw["pos_list"] = [np.array(p) for p in r["pos"]]
         kind, payload = r["sam"]
-        m = getattr(self.ns, r["cls"])(payload if kind == "host" else np.zeros_like(r["ref"]), r["ref"], **kw)
+        if self.borrowed:
+            m = getattr(self.ns, r["cls"])(_device_frames(np.array(payload)), _device_frames(np.array(r["ref"])), **kw)
+        else:
+            m = getattr(self.ns, r["cls"])(payload if kind == "host" else np.zeros_like(r["ref"]), r["ref"], **kw)
         m._force = r["force"]
         if r["Nw"] is not None:
             m.Nw = r["Nw"]
@@ -118,6 +127,16 @@ class LongLived:
         plain = raw.dtype == np.float64 and dark is None and flat is None and self.rec["unwarp"] is None
         self.rec["sam"] = ("host", np.ascontiguousarray(raw)) if plain else ("staged", (raw, dark, flat))
 
+    def write(self, sam=None, ref=None):
+        """a borrowed model's stacks rewritten where they lie: the addresses stay, the contents change"""
+        import torch
+        for key, frames, new in (("sam", self.live._sam, sam), ("ref", self.live._ref, ref)):
+            if new is not None:
+                for d, x in zip(frames, new):
+                    d.copy_(torch.from_numpy(np.array(x)))
+                self.rec[key] = ("host", np.ascontiguousarray(new)) if key == "sam" else np.ascontiguousarray(new)
+        torch.cuda.synchronize()
+
     def unwarp(self, umap):
         self.live.set_unwarp(umap)
         self.rec["unwarp"] = umap
@@ -136,13 +155,14 @@ class LongLived:
         assert path == self._path(twin), "%s: last_path %d, the fresh model's %d" % (tag, path, self._path(twin))
         if expect_path is not None:
             assert path == expect_path, "%s: last_path %d, expected %d" % (tag, path, expect_path)
-        if need is None:
-            need = ("f", "T", "dx", "dy", "err") + (("df",) if self.rec["cls"] == "UMPAModelDF" else ())
-            need += ("debug_Ncalls",) if self.rec["debug"] else ()
-        _assert_same(got, want, need, tag)
+        _assert_same(got, want, self._maps() if need is None else need, tag)
         assert roi == twin.ROI, "%s: ROI %r, the fresh model's %r" % (tag, roi, twin.ROI)
         self.rec["ROI"] = twin.ROI
         return got
+
+    def _maps(self):
+        need = ("f", "T", "dx", "dy", "err") + (("df",) if self.rec["cls"] == "UMPAModelDF" else ())
+        return need + (("debug_Ncalls",) if self.rec["debug"] else ())
 
     def match(self, what="", expect_path=None, **kw):
         got = _copy(self.live.match(quiet=True, **kw))
@@ -164,6 +184,31 @@ class LongLived:
         got = _copy(self.live.cost_volume(**kw))
         return self._check(got, self._path(self.live), self.live.ROI, lambda m: m.cost_volume(**kw), "cost_volume %r" % (kw,),
                            need=("cost",) + (("T", "df") if kw.get("with_fit") else ()))
+
+    def smooth(self, what="", **kw):
+        """smooth.match_smooth(model, lam=..., trunc=..., **kw): the start field, its margin and valid, and the maps"""
+        from umpa_amd import smooth
+        assert "lam" in kw and "trunc" in kw                          # stated by the caller: no step depends on the defaults
+        got = _copy(smooth.match_smooth(self.live, **kw))
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: smooth.match_smooth(m, **kw),
+                           what or "match_smooth %r" % (kw,), need=self._maps() + ("start", "margin", "valid"))
+
+    def uncertainty(self, result_kw, what="", smooth_kw=None, sam=None, **kw):
+        """model.uncertainty(model.match(**result_kw), **kw) -- or of smooth.match_smooth(model, **smooth_kw) --: unit, s2, dof,
+        valid.  `sam`: the stack handed to the live model as sam=; the twin gets it only where its own stack was staged
+        through a kernel too (a twin BUILT on the stack needs none: that is the comparison)."""
+        from umpa_amd import smooth
+
+        def call(m, sam_kw):
+            res = m.match(quiet=True, **result_kw) if smooth_kw is None else smooth.match_smooth(m, **smooth_kw)
+            u = m.uncertainty(res, **sam_kw, **kw)
+            return {"unit": u.unit, "s2": u.s2, "dof": u.dof, "valid": u.valid}
+
+        given = {} if sam is None else {"sam": sam}
+        got = _copy(call(self.live, given))
+        twin_kw = given if self.rec["sam"][0] == "staged" else {}
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: call(m, twin_kw),
+                           what or "uncertainty %r %r" % (result_kw if smooth_kw is None else smooth_kw, kw), need=("unit", "s2", "dof", "valid"))
 
     def report(self):
         print("\n[long-lived] %s: %d match steps compared, last_path values %s" % (self.label, self.steps, sorted(set(self.paths))))
@@ -493,3 +538,204 @@ def test_streaming_matcher_used_more_than_once(hip_ns, unwarp):
             _assert_same(got, exp, ("f", "T", "dx", "dy", "df", "err"), "8 streaming %s, projection %r" % (what, pid))
     assert not np.array_equal(want[0][1]["dx"], want[2][1]["dx"])     # (the projections differ: a mix-up would show)
     print("\n[long-lived] 8 streaming %s: %d projections compared" % ("unwarp" if unwarp else "plain", 2 * len(want)))
+
+
+# ----------------------------------------------------------------------------- 9. a staged stack and whoever reads it first
+
+_penalties = {}
+
+
+def _smooth_kw(hip_ns):
+    """lam and trunc for every match_smooth step of this file: 0.3 and 2.5 times cost_scale of the first stack's volume on
+    ROI_IN (the factors of test_match_smooth), computed once"""
+    if not _penalties:
+        from umpa_amd import smooth
+        sam, ref = _stack(5)
+        m = hip_ns.UMPAModelDF(sam, ref, window_size=WS1, max_shift=MS1)
+        unit = smooth.cost_scale(m.cost_volume(ROI=ROI_IN)["cost"])
+        assert unit > 0
+        _penalties.update(lam=0.3 * unit, trunc=2.5 * unit)
+    return dict(_penalties)
+
+
+def _consume(hip_ns, t, name, what):
+    """the calls that read the sample stack besides the walk"""
+    if name == "cost_volume":
+        return t.cost_volume(ROI=ROI_IN)
+    if name == "grid_search":
+        return t.match("grid search, " + what, ROI=FULL, search="grid")
+    return t.smooth("match_smooth, " + what, ROI=FULL, **_smooth_kw(hip_ns))
+
+
+@pytest.mark.parametrize("consumer", ["cost_volume", "grid_search", "match_smooth"])
+@pytest.mark.parametrize("raws", ["float64", "uint16"])
+@pytest.mark.parametrize("cls", ["UMPAModelDF", "UMPAModelNoDF"])
+def test_a_staged_stack_is_adopted_by_whoever_reads_the_sample_stack_first(hip_ns, cls, raws, consumer):
+    """The consumer on a fresh live model: stage, the consumer, match(), the consumer again.  float64 raws
+    without dark and flat are copied as they are, so the twin is BUILT on them; uint16 counts with dark and flat go through the
+    flat-correction kernel, and the twin stages the same.  (Where cost_volume() does not adopt the staged stack, the first
+    step of "cost_volume" and of "match_smooth" returns the constructor's stack's volume / start field.)"""
+    samA, refA = _stack(5)
+    samB, _ = _stack(9, amplitude=2.0)
+    if raws == "uint16":
+        rng = np.random.default_rng(3)
+        dark = 100.0 + rng.uniform(0, 2, size=samA.shape)
+        flat = 20000.0 * (1.0 + 0.05 * rng.standard_normal(samA.shape))
+        staged = dict(raw=_counts(samB, flat, dark), dark=_device_frames(dark), flat=_device_frames(flat))
+    else:
+        staged = dict(raw=np.ascontiguousarray(samB))
+    t = LongLived(hip_ns, cls, samA, refA, WS1, MS1, label="9 staged %s, %s first, %s" % (raws, consumer, cls))
+    t.stage(**staged)
+    _consume(hip_ns, t, consumer, "first after stage_sample")
+    assert not t.live._use_staged                                     # adopted: the one-shot bit is spent
+    t.match("the walk after it", ROI=FULL)
+    _consume(hip_ns, t, consumer, "again")
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 10. the last stack wins
+
+@pytest.mark.parametrize("cls", ["UMPAModelDF", "UMPAModelNoDF"])
+def test_the_last_stack_wins_between_stage_sample_and_update_frames(hip_ns, cls):
+    from umpa_amd import _lib
+    samA, refA = _stack(5)
+    samB, refB = _stack(9, amplitude=2.0)
+    samC, _ = _stack(13)
+    t = LongLived(hip_ns, cls, samA, refA, WS1, MS1, label="10 last stack wins " + cls)
+    t.match("as built", ROI=FULL)
+    t.stage(np.ascontiguousarray(samB))
+    t.update(sam=samC)                                                # the record's sample stack is samC now
+    t.match("stage_sample, update_frames(sam): the update is the later stack", ROI=FULL)
+    # the library's own rule, past the Python bookkeeping: the dropped stack cannot be asked for
+    t.live._use_staged = True
+    with pytest.raises(_lib.NativeError, match="UMPA_HIP_F_USE_STAGED without a staged sample stack"):
+        t.live.match(quiet=True, ROI=FULL)
+    assert not t.live._use_staged
+    t.match("the same again after the refused flag", ROI=FULL)
+    t.stage(np.ascontiguousarray(samA))
+    t.match("one more stage_sample: a first swap, the dropped stack's buffer is overwritten", ROI=FULL)
+    t.stage(np.ascontiguousarray(0.5 * samB))
+    t.match("... and a second swap: the dropped stack does not come back", ROI=FULL)
+    t.stage(np.ascontiguousarray(samB))
+    t.update(ref=refB)                                                # the reference alone: the staged stack stays pending
+    assert t.live._use_staged
+    t.match("stage_sample, update_frames(ref): the staged stack with the new reference", ROI=FULL)
+    t.stage(np.ascontiguousarray(samC))
+    t.match("one more stage_sample", ROI=ROI_OUT)
+    t.stage(np.ascontiguousarray(samB))
+    t.update(sam=samA, ref=refA)
+    t.cost_volume(ROI=ROI_IN)                                         # the same rule for the volume
+    t.match("stage_sample, update_frames(both), cost_volume: the walk after them", ROI=FULL)
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 11. uncertainty() over time
+
+@pytest.mark.parametrize("cls", ["UMPAModelDF", "UMPAModelNoDF"])
+def test_uncertainty_over_time(hip_ns, cls):
+    samA, refA = _stack(5)
+    samB, refB = _stack(9, amplitude=2.0)
+    samC, refC = _stack(13)
+    t = LongLived(hip_ns, cls, samA, refA, WS1, MS1, label="11 uncertainty " + cls)
+    first = t.uncertainty(dict(ROI=FULL), "as built")
+    assert first["valid"].mean() > 0.5                                # (the maps are there to be compared)
+    t.update(sam=samB)
+    after_sam = t.uncertainty(dict(ROI=FULL), "update_frames(sam)")
+    assert not np.array_equal(after_sam["unit"], first["unit"], equal_nan=True)     # (the stacks differ: a stale one would show)
+    t.update(ref=refB)
+    t.uncertainty(dict(ROI=FULL), "update_frames(ref)")
+    t.update(sam=samC, ref=refC)
+    t.uncertainty(dict(ROI=FULL), "update_frames(both)")
+    # the default region is the ROI the match left behind
+    part = t.uncertainty(dict(ROI=ROI_IN), "default region after match(ROI=ROI_IN)")
+    assert part["unit"].shape == (3, 16, 20)
+    whole = t.uncertainty(dict(ROI=FULL), "default region after match(ROI=FULL)")
+    assert whole["unit"].shape == (3,) + (FULL[0][1], FULL[1][1])
+    t.uncertainty(None, "after match_smooth(ROI=ROI_OUT)", smooth_kw=dict(ROI=ROI_OUT, **_smooth_kw(hip_ns)))
+    t.uncertainty(None, "after match_smooth on a stepped ROI", smooth_kw=dict(ROI=((3, 100, 2), (5, 120, 3)), **_smooth_kw(hip_ns)))
+    # a narrower window is refused by name; back at the constructor's window the maps are a fresh model's
+    t.set(Nw=3)
+    res = t.match("Nw 3", ROI=FULL)
+    with pytest.raises(RuntimeError, match="uncertainty: a window narrower than the one the model was built with is not supported"):
+        t.live.uncertainty(res)
+    t.set(Nw=WS1)
+    t.uncertainty(dict(ROI=FULL), "Nw back at the constructor's window")
+    t.report()
+
+
+@pytest.mark.parametrize("cls", ["UMPAModelDF", "UMPAModelNoDF"])
+def test_uncertainty_under_a_borrowed_stack_rewritten_in_place(hip_ns, cls):
+    """the pattern of test_hip_borrowed.py::test_stacks_rewritten_in_place_under_one_borrowed_model: the frame addresses of the
+    live model never change, their contents do; uncertainty() reads the planes where they lie"""
+    from umpa_amd import sigma
+    samA, refA = _stack(5)
+    samB, refB = _stack(9, amplitude=2.0)
+    t = LongLived(hip_ns, cls, samA, refA, WS1, MS1, label="12 uncertainty, borrowed " + cls, borrowed=True)
+    base = t.live._sam[0].data_ptr()
+    assert sigma._stack(t.live._sam).data_ptr() == base               # borrowed as it lies, not stacked into a copy
+    first = t.uncertainty(dict(ROI=FULL), "as built")
+    t.write(sam=samB)
+    after_sam = t.uncertainty(dict(ROI=FULL), "sample stack overwritten in place")
+    assert not np.array_equal(after_sam["unit"], first["unit"], equal_nan=True)
+    t.write(ref=refB)
+    t.uncertainty(dict(ROI=FULL), "reference stack overwritten in place")
+    t.uncertainty(dict(ROI=ROI_IN), "a ROI")
+    t.write(sam=samA, ref=refA)
+    back = t.uncertainty(dict(ROI=FULL), "the first stacks again")
+    _assert_same(back, first, ("unit", "s2", "dof", "valid"), "12 borrowed %s: the first data gives the first maps again" % cls)
+    assert t.live._sam[0].data_ptr() == base
+    t.report()
+
+
+# ----------------------------------------------------------------------------- 13. uncertainty() after stage_sample
+
+@pytest.mark.parametrize("cls", ["UMPAModelDF", "UMPAModelNoDF"])
+def test_uncertainty_after_stage_sample_takes_the_stack_as_an_argument(hip_ns, cls):
+    """The model keeps no host copy of a staged stack (it exists flat-corrected in the library's buffer only), so
+    uncertainty() refuses by name until it is given the stack -- a host array or a HIP tensor -- or update_frames(sam_list=...)
+    gives the model one again.  (Without the refusal the call reads the constructor's stack: finite maps of the wrong frames.)"""
+    import torch
+    from umpa_amd import sigma
+    samA, refA = _stack(5)
+    samB, _ = _stack(9, amplitude=2.0)
+    samC, _ = _stack(13)
+    refusal = re.escape("uncertainty: the sample stack was staged (stage_sample); pass it as sam=")
+    t = LongLived(hip_ns, cls, samA, refA, WS1, MS1, label="13 uncertainty, staged " + cls)
+    t.uncertainty(dict(ROI=FULL), "as built")
+    t.stage(np.ascontiguousarray(samB))
+    res = t.match("stage_sample float64", ROI=FULL)
+    with pytest.raises(RuntimeError, match=refusal):
+        t.live.uncertainty(res)
+    on_host = t.uncertainty(dict(ROI=FULL), "sam= a host array, against a model built on it", sam=np.ascontiguousarray(samB))
+    on_dev = t.uncertainty(dict(ROI=FULL), "sam= a HIP tensor", sam=torch.from_numpy(np.array(samB)).to("cuda:0"))
+    _assert_same(on_dev, on_host, ("unit", "s2", "dof", "valid"), "13 %s: device and host sam=" % cls)
+    # ... and the library call on the same shift field
+    kind = int(cls == "UMPAModelDF")
+    reg = (0, 1, FULL[0][1], 0, 1, FULL[1][1])
+    direct = sigma.region(np.ascontiguousarray(samB), refA, t.live.window, MS1, kind, reg, sigma.shift_field(res, MS1))
+    for k in ("unit", "s2", "dof"):
+        assert np.array_equal(on_host[k], direct[k], equal_nan=True), k
+    # the argument is checked by name
+    with pytest.raises(ValueError, match=r"sam must be \[K, H, W\] = \(6, 120, 140\)"):
+        t.live.uncertainty(res, sam=np.ascontiguousarray(samB[:, :-1]))
+    with pytest.raises(ValueError, match=r"sam must be \[K, H, W\]"):
+        t.live.uncertainty(res, sam=torch.zeros((K1 - 1, H1, W1), dtype=torch.float64, device="cuda:0"))
+    with pytest.raises(ValueError, match="sam must be float64"):
+        t.live.uncertainty(res, sam=samB.astype(np.float32))
+    # a second staged stack, not adopted yet: still refused
+    t.stage(np.ascontiguousarray(samA))
+    with pytest.raises(RuntimeError, match=refusal):
+        t.live.uncertainty(res)
+    t.update(sam=samC)                                                # the model holds its sample stack again
+    t.uncertainty(dict(ROI=FULL), "update_frames(sam) after stage_sample: no argument needed")
+    # uint16 counts with dark and flat: the twin stages the same and is refused the same; both take the same sam=
+    rng = np.random.default_rng(3)
+    dark = 100.0 + rng.uniform(0, 2, size=samA.shape)
+    flat = 20000.0 * (1.0 + 0.05 * rng.standard_normal(samA.shape))
+    counts = _counts(samB, flat, dark)
+    t.stage(counts, dark=_device_frames(dark), flat=_device_frames(flat))
+    res = t.match("stage_sample uint16 with dark and flat", ROI=FULL)
+    with pytest.raises(RuntimeError, match=refusal):
+        t.live.uncertainty(res)
+    t.uncertainty(dict(ROI=FULL), "sam= after a flat-corrected stage_sample", sam=(counts - dark) / flat)
+    t.report()

@@ -271,3 +271,32 @@ def test_match_smooth_refuses_what_cost_volume_refuses(smooth, noisy_stack):
     with pytest.raises(ValueError, match="lam must be >= 0"):
         smooth.match_smooth(ok, lam=-1.0, trunc=2.0)
     assert smooth.match_smooth(ok, lam=1e-3, trunc=1e-2)["start"].shape == (2, 80, 96)   # and it still works afterwards
+
+
+def test_a_workspace_beyond_the_free_device_memory_is_refused(smooth):
+    """U = 15 on 2^20 x 2^20 pixels, 1.9 PB per volume, claimed for two tensors of 64 elements.  The size check sits before
+    every allocation and launch: the call returns UMPA_HIP_E_UNSUPPORTED and names the bytes needed and the bytes free.  Were
+    the check broken, the first hipMalloc of a volume would fail instead (UMPA_HIP_E_NOMEM): either way no kernel can run on
+    the short tensors, so this test cannot write out of bounds."""
+    import re
+    import torch
+    from umpa_amd import _lib
+    lib = _lib.smooth()
+    U, N = 15, 1 << 20
+    vol = U * U * N * N * 8
+    assert lib.workspace_bytes(U, N, N, 0xFF) == 3 * vol
+    cost = torch.zeros(64, dtype=torch.float64, device="cuda:0")
+    shift = torch.full((64,), 7, dtype=torch.int32, device="cuda:0")
+    rc = lib.aggregate(cost.data_ptr(), U, N, N, 1.0, 2.0, 0xFF, shift.data_ptr(), None, None, None, None, 0, _lib.F_DEVICE_IO, None)
+    assert rc == -4, (rc, lib.error())                               # UMPA_HIP_E_UNSUPPORTED
+    said = re.search(r"smooth: (\d+) bytes of device memory needed for a 15 x 15 x 1048576 x 1048576 volume, (\d+) free", lib.error())
+    assert said, lib.error()
+    need, free = int(said.group(1)), int(said.group(2))
+    assert need == 3 * vol and 0 < free < need
+    torch.cuda.synchronize()
+    assert (shift == 7).all() and (cost == 0).all()
+    # and the library still works: a small volume against the restatement
+    small = SE.with_specials(SE.random_volume(5, 19, 23, 5), 105)
+    host = _check(smooth, small, 0.5, 2.25, "after the refusal")
+    on_dev = smooth.aggregate(torch.from_numpy(small).cuda(), 0.5, 2.25, return_total=True)
+    _equal({k: v.cpu().numpy() for k, v in on_dev.items()}, host, "after the refusal, device arrays")

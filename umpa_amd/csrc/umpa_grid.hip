@@ -105,7 +105,10 @@ UMPA_GRID_API int umpa_grid_cost_volume(umpa_hip_model* m, int start0, int step0
                                         double* cost, double* T, double* df, int flags, void* stream)
 {
     if (!m || !cost) return fail(UMPA_HIP_E_ARG, "grid: null argument");
-    if (flags & ~UMPA_HIP_F_DEVICE_IO) return fail(UMPA_HIP_E_ARG, "grid: cost_volume takes UMPA_HIP_F_DEVICE_IO and no other flag");
+    if (flags & ~(UMPA_HIP_F_DEVICE_IO | UMPA_HIP_F_USE_STAGED))
+        return fail(UMPA_HIP_E_ARG, "grid: cost_volume takes UMPA_HIP_F_DEVICE_IO, UMPA_HIP_F_USE_STAGED and no other flag");
+    // a staged sample stack is adopted by the match entry point underneath, as by any match: the volume is then that stack's
+    const int staged = flags & UMPA_HIP_F_USE_STAGED;
     GridJob J;
     J.volume = true;
     // the match entry point wants value and status arrays; this consumer's kernel touches neither, and with device I/O the
@@ -117,13 +120,13 @@ UMPA_GRID_API int umpa_grid_cost_volume(umpa_hip_model* m, int start0, int step0
         J.V.cost = cost; J.V.T = T; J.V.df = df;
         J.want[2] = df != nullptr;
         return run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
-                   UMPA_HIP_F_DEVICE_IO, stream);
+                   UMPA_HIP_F_DEVICE_IO | staged, stream);
     }
     // host arrays: device copies for the duration of the call, allocated by the consumer (the model's device is current
     // there and stays this thread's current device afterwards), filled on that device's null stream
     J.host = true; J.want[0] = true; J.want[1] = T != nullptr; J.want[2] = df != nullptr;
     int rc = run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
-                 UMPA_HIP_F_DEVICE_IO, nullptr);
+                 UMPA_HIP_F_DEVICE_IO | staged, nullptr);
     double* const host[3] = {cost, T, df};
     hipError_t e = hipSuccess;
     for (int q = 0; q < 3 && rc >= 0 && e == hipSuccess; q++)

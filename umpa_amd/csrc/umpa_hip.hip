@@ -781,6 +781,9 @@ int umpa_hip_update_frames(umpa_hip_model* m, double* const* sam, double* const*
     if (!m->owns_frames) return fail(UMPA_HIP_E_ARG, "the model borrows device frames; update them in place instead");
     HIP_TRY(hipSetDevice(m->device), UMPA_HIP_E_DEVICE);
     if (ref) m->tiled.ref_maps_ok = false;
+    // the last stack wins: a stack staged before this call and not adopted yet is dropped (its upload may still be running
+    // into the back buffer, which nothing reads before the next umpa_hip_stage_sample)
+    if (sam) m->staged = false;
     for (int k = 0; k < m->Na; k++) {
         const size_t n = (size_t)m->dims[2 * k] * m->dims[2 * k + 1] * sizeof(double);
         if (sam) HIP_TRY(hipMemcpyAsync(m->d_sam[k], sam[k], n, hipMemcpyHostToDevice, m->stream), UMPA_HIP_E_DEVICE);

@@ -169,7 +169,8 @@ class UMPAModelBase:
     def update_frames(self, sam_list=None, ref_list=None):
         """Swap in new sample and/or reference stacks of the same shapes without rebuilding the model
         (extension: the reference rebuilds a model per projection, ``umpa_multi.py:149``).  On the GPU
-        the untouched stack stays resident."""
+        the untouched stack stays resident.  The last stack wins: a sample stack given here drops one that ``stage_sample``
+        uploaded and no call has adopted yet; ``ref_list`` alone leaves it pending."""
         new_sam = self._prepare_frames(sam_list) if sam_list is not None else None
         new_ref = self._prepare_frames(ref_list) if ref_list is not None else None
         for new in (new_sam, new_ref):
@@ -183,6 +184,7 @@ class UMPAModelBase:
                                                 fs_r.table if fs_r else None), "update_frames")
         if new_sam is not None:
             self._sam, self._sam_list = new_sam, sam_list
+            self._use_staged = self._sam_staged = False            # (the library dropped a pending staged stack too)
         if new_ref is not None:
             self._ref, self._ref_list = new_ref, ref_list
         self._fs = (_lib.FrameSet(self._sam), _lib.FrameSet(self._ref), self._fs[2])
@@ -450,7 +452,7 @@ class UMPAModelBase:
         vp = lambda k: out[k].ctypes.data if k in out else None
         try:
             _lib.grid().check(_lib.grid().cost_volume(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1,
-                                                      vp('cost'), vp('T'), vp('df'), 0, None), "grid cost_volume")
+                                                      vp('cost'), vp('T'), vp('df'), self._staged_flag(), None), "grid cost_volume")
         except _lib.NativeError as e:
             raise RuntimeError("cost_volume: %s" % e) from None
         return out
@@ -460,7 +462,8 @@ class UMPAModelBase:
         ``cost[U, U, N0, N1]``, ``U = 2 max_shift - 1``, where ``cost[si + max_shift - 1, sj + max_shift - 1, xi, xj]``
         is ``cost(i, j, si, sj)[0]`` of the region's pixel ``(xi, xj)`` (``si``: row shift, ``sj``: column shift) -- the
         numbers ``match()`` compares, bit for bit.  ``with_fit=True`` adds ``T`` and, for the dark-field model, ``df`` in
-        the same layout.  ``ROI`` / ``step`` as for ``match()``; the model's own ROI is not changed.
+        the same layout.  ``ROI`` / ``step`` as for ``match()``; the model's own ROI is not changed.  A stack uploaded by
+        ``stage_sample`` and not adopted yet is adopted by this call, as by ``match()``: the volume is that stack's.
 
         Mind the size: an array holds ``U * U * N0 * N1`` doubles -- 2.7 GB for a whole 2048 x 2048 image at
         ``max_shift=5`` -- so a ``ROI`` of the rows or the patch in question is the normal use.
@@ -470,6 +473,7 @@ class UMPAModelBase:
 
     _force = 0
     _use_staged = False
+    _sam_staged = False         # the sample stack came from stage_sample: self._sam is not the stack the library matches
     _async = False
     _out_alloc = None           # hook (shape, dtype, zero) -> array for the result maps (farm.py: shared-memory result slots)
 
@@ -490,21 +494,28 @@ class UMPAModelBase:
     def wait(self):
         self._lib.check(self._lib.wait(self._handle), "wait")
 
+    def _staged_flag(self):
+        """F_USE_STAGED once after stage_sample: the staged stack is adopted by the call that is given it"""
+        if not self._use_staged:
+            return 0
+        self._use_staged = False
+        return _lib.F_USE_STAGED
+
     def _match_flags(self):
         f = self._force
         if self._async:
             f |= _lib.F_ASYNC
-        if self._use_staged:                                        # one-shot: the staged stack is adopted by this match
-            f |= _lib.F_USE_STAGED
-            self._use_staged = False
-        return f
+        return f | self._staged_flag()
 
     def stage_sample(self, raw_frames, dark=None, flat=None):
         """Upload the NEXT sample stack while the current match is still running (extension; the reference builds a
         new model per projection, ``umpa_multi.py:149``).  ``raw_frames``: host frames of the model's shapes, float64 /
         float32 / uint16 (page-locked arrays -- ``_lib.pinned_empty`` -- make this return at once); ``dark`` / ``flat``:
         device float64 stacks (lists of 2-D HIP tensors) for the fused ``(raw - dark) / flat`` of ``umpa_multi.py:144``.
-        The staged stack becomes the sample stack of the next ``match()``."""
+        The staged stack becomes the sample stack of the next call that reads the sample stack -- ``match()``,
+        ``cost_volume()``, ``match_smooth`` -- and stays it.  The last stack wins: another ``stage_sample`` or
+        ``update_frames(sam_list=...)`` before that call replaces it.  The model keeps no host copy of a staged stack:
+        ``uncertainty()`` then needs it as ``sam=``."""
         if not self._lib.is_hip or hasattr(self._sam[0], "data_ptr"):
             raise RuntimeError('stage_sample needs a model that owns device copies of host frames.')
         raw = [np.asarray(x) for x in raw_frames]
@@ -520,7 +531,7 @@ class UMPAModelBase:
         self._lib.check(self._lib.stage_sample(self._handle, fs.table, code, fd.table if fd else None,
                                                ff.table if ff else None), "stage_sample")
         self._staged_keep = (raw, dark, flat)                       # alive until the upload has been consumed
-        self._use_staged = True
+        self._use_staged = self._sam_staged = True
 
     def set_unwarp(self, unwarp_map):
         """Attach an ``umpa_amd.unwarp.UnwarpMap`` (or detach with None): while one is attached, ``stage_sample`` resamples
@@ -676,10 +687,10 @@ class UMPAModelNoDF(UMPAModelBase):
         return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
     cost_volume.__doc__ = UMPAModelBase._COST_VOLUME_DOC
 
-    def uncertainty(self, result, noise_var=None, ROI=None, step=None):
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
         """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
         from . import sigma
-        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step)
+        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step, sam=sam)
 
 
 class UMPAModelDF(UMPAModelBase):
@@ -710,10 +721,10 @@ class UMPAModelDF(UMPAModelBase):
         return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
     cost_volume.__doc__ = UMPAModelBase._COST_VOLUME_DOC
 
-    def uncertainty(self, result, noise_var=None, ROI=None, step=None):
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
         """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
         from . import sigma
-        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step)
+        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step, sam=sam)
 
     @property
     def Im(self):
@@ -761,5 +772,5 @@ class UMPAModelDFKernel(UMPAModelBase):
                              num_threads=num_threads, quiet=quiet)
         return self._unpack(result, False)
 
-    def uncertainty(self, result, noise_var=None, ROI=None, step=None):
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
         raise RuntimeError("uncertainty: the kernel dark-field model is not supported")

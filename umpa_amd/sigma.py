@@ -192,11 +192,36 @@ def _stack(frames):
     return torch.stack(list(frames))
 
 
-def uncertainty(model, result, noise_var=None, ROI=None, step=None):
+def _given_stack(model, sam):
+    """The caller's sample stack in place of model._sam: [K, H, W] float64, a host array or a contiguous HIP tensor on the
+    model's device, of the model's frames' shape."""
+    shape = (len(model._sam),) + tuple(int(v) for v in model._sam[0].shape)
+    if hasattr(sam, "data_ptr"):
+        import torch
+        if not sam.is_cuda or sam.device.index != model._device:
+            raise ValueError("sam must be a host array or a HIP tensor on the model's device %d, not on %s" % (model._device, sam.device))
+        if sam.dtype != torch.float64:
+            raise ValueError("sam must be float64, not %s" % sam.dtype)
+        if not sam.is_contiguous():
+            raise ValueError("sam must be contiguous")
+    else:
+        sam = np.asarray(sam)
+        if sam.dtype != np.float64:
+            raise ValueError("sam must be float64, not %s" % sam.dtype)
+        sam = np.ascontiguousarray(sam)
+    if tuple(sam.shape) != shape:
+        raise ValueError("sam must be [K, H, W] = %r as the model's stack, not %r" % (shape, tuple(sam.shape)))
+    return sam
+
+
+def uncertainty(model, result, noise_var=None, ROI=None, step=None, sam=None):
     """The uncertainty maps of ``result = model.match(...)``: an ``Uncertainty``.
 
     The model supplies its stacks and its window (host frames are uploaded by the call, HIP tensors are read where they
-    lie), ``result`` the shift field (``shift_field``).  ``ROI`` / ``step`` as for ``match()``; the default is the model's
+    lie), ``result`` the shift field (``shift_field``).  ``sam``: the sample stack to use in place of the model's own,
+    ``[K, H, W]`` float64, a host array or a contiguous HIP tensor on the model's device -- required after
+    ``stage_sample``, whose stack (flat-corrected on the device) the model keeps no host copy of: without it the call
+    raises ``RuntimeError`` until ``update_frames(sam_list=...)`` gives the model a stack again.  ``ROI`` / ``step`` as for ``match()``; the default is the model's
     current ROI, which ``match()`` left at the region of ``result``.  ``noise_var``: the variance of ``sam - model``, i.e.
     ``sigma_sam^2 + T^2 sigma_ref^2``, where it is known; by default the variances are scaled with ``s2``, which at low noise
     also contains interpolation and model misfit and is then an upper estimate.
@@ -212,9 +237,17 @@ def uncertainty(model, result, noise_var=None, ROI=None, step=None):
     model._check_range(s0, s1, N0, N1)
     if tuple(np.shape(result["dx"])) != (N0, N1):
         raise ValueError("the maps of result are %r, the region has %d x %d pixels" % (tuple(np.shape(result["dx"])), N0, N1))
+    if sam is not None:
+        sam = _given_stack(model, sam)
+    elif model._sam_staged:
+        raise RuntimeError("uncertainty: the sample stack was staged (stage_sample); pass it as sam=")
     shift = shift_field(result, model._max_shift)
-    sam, ref = _stack(model._sam), _stack(model._ref)
+    sam, ref = _stack(model._sam) if sam is None else sam, _stack(model._ref)
     reg = (s0[0], s0[2], N0, s1[0], s1[2], N1)
+    if hasattr(sam, "data_ptr") != hasattr(ref, "data_ptr"):          # a given stack on the other side: both onto the device
+        import torch
+        dev = torch.device("cuda", model._device)
+        sam, ref = (torch.from_numpy(x).to(dev) if not hasattr(x, "data_ptr") else x for x in (sam, ref))
     if hasattr(sam, "data_ptr"):
         import torch
         with torch.cuda.device(sam.device):

@@ -132,7 +132,8 @@ def cost_scale(cost):
 def match_smooth(model, lam=None, trunc=None, paths=8, ROI=None, step=None, quiet=True):
     """``model.match()`` started, pixel by pixel, from the regularised integer shift field of the model's own cost volume.
 
-    The volume is computed on the device (``umpa_grid_cost_volume``) and stays there; ``lam`` and ``trunc`` default to
+    The volume is computed on the device (``umpa_grid_cost_volume``) and stays there (a stack uploaded by ``stage_sample``
+    is adopted by that call, so the volume and the match read the same stack); ``lam`` and ``trunc`` default to
     ``LAM_REL`` and ``TRUNC_REL`` times ``cost_scale`` of it.  Returns the dictionary of
     ``model.match(dxdy=(start[0], start[1]), ROI=..., step=...)`` plus ``start`` (``[2, N0, N1]`` int32), ``margin``
     (``aggregate``), ``valid`` and the penalties used, ``lam`` and ``trunc``.
@@ -156,7 +157,7 @@ def match_smooth(model, lam=None, trunc=None, paths=8, ROI=None, step=None, quie
         stream = torch.cuda.current_stream(dev).cuda_stream
         try:
             _lib.grid().check(_lib.grid().cost_volume(model._handle, s0[0], s0[2], N0, s1[0], s1[2], N1, cost.data_ptr(), None, None,
-                                                      _lib.F_DEVICE_IO, stream), "grid cost_volume")
+                                                      _lib.F_DEVICE_IO | model._staged_flag(), stream), "grid cost_volume")
         except _lib.NativeError as e:
             raise RuntimeError("cost_volume: %s" % e) from None
         if lam is None or trunc is None:
