@@ -257,24 +257,57 @@ def sigma():
     return _satellite("sigma", _SIGMA_ABI)
 
 
-def device_io(*tensors):
-    """``(device index, stream handle)`` for a call on HIP tensors (``None`` entries are skipped): the tensors' device and
-    the caller's current stream on it.  They must be contiguous and on one HIP device."""
-    import torch
-    given = [t for t in tensors if t is not None]
-    for t in given:
-        if not t.is_contiguous() or not t.is_cuda or t.device != given[0].device:
-            raise ValueError("device arrays must be contiguous HIP tensors on one device")
-    d = given[0].device
-    return d.index if d.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(d).cuda_stream
-
-
 def host_device(device):
     """The device index of a call on host arrays: ``device``, or the package's default for ``None``."""
     if device is None:
         from . import model
         return model._default_device()
     return int(device)
+
+
+class Side:
+    """The side a binding call is on, decided once from its arrays (``None`` entries are skipped) and its ``device=``
+    keyword: host arrays, which the library copies to ``device`` and back, or HIP tensors, which it works on where they
+    lie, on the caller's current stream.  The first array decides; with ``mixed`` (a module's refusal text) a call that
+    has arrays of both sides is refused with it.
+
+    ``on_device`` is for the few lines that differ per side on purpose (host arrays are converted where a tensor of a
+    wrong dtype is refused).  Allocation, pointers and the end of the native call are spelled here only."""
+
+    def __init__(self, *arrays, device=None, mixed=None):
+        self._arrays = [a for a in arrays if a is not None]
+        sides = [hasattr(a, "data_ptr") for a in self._arrays]
+        if mixed is not None and any(sides) and not all(sides):
+            raise ValueError(mixed)
+        self.on_device, self._device = sides[0], device
+
+    def empty(self, shape, dtype):
+        """An uninitialised output of a numpy ``dtype`` on the call's side (on the first tensor's device)."""
+        import numpy as np
+        if not self.on_device:
+            return np.empty(shape, dtype=dtype)
+        import torch
+        return torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=self._arrays[0].device)
+
+    @staticmethod
+    def ptr(a):
+        """The address of an array or a tensor; ``None`` for ``None``.  (Per array, not per side: the small host arrays
+        some calls take or fill beside tensors -- a window, iteration counts -- go through here too.)"""
+        if a is None:
+            return None
+        return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+    def tail(self, flags=0):
+        """``(device, flags, stream)``, the last three arguments of every satellite call.  For tensors this is where they
+        are checked: contiguous and on one HIP device, whose index and current stream the call gets with ``F_DEVICE_IO``."""
+        if not self.on_device:
+            return host_device(self._device), flags, None
+        import torch
+        d = self._arrays[0].device
+        for t in self._arrays:
+            if not t.is_contiguous() or not t.is_cuda or t.device != d:
+                raise ValueError("device arrays must be contiguous HIP tensors on one device")
+        return d.index if d.index is not None else torch.cuda.current_device(), F_DEVICE_IO | flags, torch.cuda.current_stream(d).cuda_stream
 
 
 ROWS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)       # umpa_hip_rows_fn

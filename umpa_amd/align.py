@@ -60,9 +60,8 @@ def correct_bad_pixels(img_in, th=None, iterations=1, dims=(-2, -1), p=0.5, devi
         raise IndexError("correct_bad_pixels: the neighbour axes need at least two entries")
     out = np.empty_like(work)
     lib = _lib.hip()
-    dev = model._default_device() if device is None else int(device)
     rc = lib.correct_bad_pixels(work.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
-                                nimg, H, W, len(axes), lo, hi, int(iterations), dev, 0, None)
+                                nimg, H, W, len(axes), lo, hi, int(iterations), _lib.host_device(device), 0, None)
     lib.check(rc, "correct_bad_pixels")
     out = np.ascontiguousarray(np.moveaxis(out, list(range(img.ndim - len(axes), img.ndim)), axes))
     return out.astype(img_in.dtype, copy=False)                       # the reference works in the input's dtype

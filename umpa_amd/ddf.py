@@ -21,13 +21,13 @@ import time
 
 import numpy as np
 
-from . import _lib
+from . import _lib, model
 
 __all__ = ["gaussian_kernel", "kernel_from_sigma", "sigma_from_kernel", "candidate_grid", "check_candidates", "blur_frames",
            "fold", "KernelSearch", "TAPS", "HALF"]
 
 TAPS, HALF = _lib.DDF_TAPS, _lib.DDF_HALF
-_vp = C.c_void_p
+_ptr = _lib.Side.ptr
 
 
 def _admissible(a, b, c):
@@ -59,7 +59,7 @@ def gaussian_kernel(a, b, c):
                          "are required" % (a, b, c))
     lib = _lib.ddf()
     g = np.empty((TAPS, TAPS), dtype=np.float64)
-    lib.check(lib.kernel(float(a), float(b), float(c), g.ctypes.data_as(_vp)), "ddf kernel")
+    lib.check(lib.kernel(float(a), float(b), float(c), _ptr(g)), "ddf kernel")
     return g
 
 
@@ -117,18 +117,21 @@ def candidate_grid(sigmas, ratios, n_angles):
 
 
 def _table(ptrs):
-    t = (_vp * len(ptrs))()
+    t = (C.c_void_p * len(ptrs))()
     for k, p in enumerate(ptrs):
         t[k] = p
     return t
 
 
-def _blur_device(frames_in, frames_out, g, dev, stream):
+def _blur(frames_in, frames_out, g, tail):
     lib = _lib.ddf()
     H, W = frames_in[0].shape
-    rc = lib.blur(_table([f.data_ptr() for f in frames_in]), _table([f.data_ptr() for f in frames_out]), len(frames_in), H, W,
-                  g.ctypes.data_as(_vp), dev, _lib.F_DEVICE_IO, stream)
+    rc = lib.blur(_table([_ptr(f) for f in frames_in]), _table([_ptr(f) for f in frames_out]), len(frames_in), H, W, _ptr(g), *tail)
     lib.check(rc, "ddf blur")
+
+
+def _blur_device(frames_in, frames_out, g, dev, stream):
+    _blur(frames_in, frames_out, g, (dev, _lib.F_DEVICE_IO, stream))
 
 
 def blur_frames(frames, abc, device=None):
@@ -138,13 +141,12 @@ def blur_frames(frames, abc, device=None):
     device) a tensor, computed on the current stream."""
     a, b, c = abc
     g = gaussian_kernel(a, b, c)
-    lib = _lib.ddf()
     single = hasattr(frames, "ndim") and frames.ndim == 2 or hasattr(frames, "dim") and frames.dim() == 2
     flist = [frames] if single else list(frames)
     if not flist:
         raise ValueError("no frames")
-    on_device = hasattr(flist[0], "data_ptr")
-    if on_device:
+    io = _lib.Side(*flist, device=device)
+    if io.on_device:
         import torch
         for f in flist:
             if not hasattr(f, "data_ptr") or f.dtype != torch.float64 or not f.is_cuda or not f.is_contiguous() or f.dim() != 2 \
@@ -157,28 +159,26 @@ def blur_frames(frames, abc, device=None):
         raise ValueError("frames of unequal shapes: %r" % ([tuple(f.shape) for f in flist],))
     if sh[0] < TAPS or sh[1] < TAPS:
         raise ValueError("frames of %d x %d pixels are smaller than the %d x %d kernel" % (sh[0], sh[1], TAPS, TAPS))
-    if on_device:
-        import torch
-        dev, stream = _lib.device_io(*flist)
-        out = torch.empty((len(flist),) + sh, dtype=torch.float64, device=flist[0].device)
-        _blur_device(flist, [out[k] for k in range(len(flist))], g, dev, stream)
-    else:
-        out = np.empty((len(flist),) + sh, dtype=np.float64)
-        rc = lib.blur(_table([f.ctypes.data for f in flist]), _table([out[k].ctypes.data for k in range(len(flist))]),
-                      len(flist), sh[0], sh[1], g.ctypes.data_as(_vp), _lib.host_device(device), 0, None)
-        lib.check(rc, "ddf blur")
+    tail = io.tail()
+    out = io.empty((len(flist),) + sh, np.float64)
+    _blur(flist, [out[k] for k in range(len(flist))], g, tail)
     return out[0] if single else out
 
 
+_FOLD_DTYPES = ["float64"] * 4 + ["int32"] + ["float64"] * 4 + ["int32"] * 2
+
+
 def fold(m, cand, best, device=None):
-    """``umpa_ddf_fold`` on host arrays: candidate ``m``'s planes ``cand = (f, T, dx, dy, err)`` into ``best = (f, T, dx, dy,
-    index, err)``, in place (float64 and int32 arrays of one size, C-contiguous)."""
+    """``umpa_ddf_fold``: candidate ``m``'s planes ``cand = (f, T, dx, dy, err)`` into ``best = (f, T, dx, dy, index, err)``,
+    in place (float64 and int32 arrays of one size, C-contiguous): host arrays, or HIP tensors on the current stream."""
     lib = _lib.ddf()
-    n = cand[0].size
-    for x, dt in list(zip(cand, [np.float64] * 4 + [np.int32])) + list(zip(best, [np.float64] * 4 + [np.int32] * 2)):
-        if x.dtype != dt or not x.flags.c_contiguous or x.size != n:
+    planes = list(cand) + list(best)
+    n = int(np.prod(cand[0].shape))
+    io = _lib.Side(*planes, device=device)
+    for x, dt in zip(planes, _FOLD_DTYPES):
+        if str(x.dtype).split(".")[-1] != dt or int(np.prod(x.shape)) != n or not (io.on_device or x.flags.c_contiguous):
             raise ValueError("fold planes must be C-contiguous float64 (int32: err, index) arrays of one size")
-    rc = lib.fold(int(m), n, *[x.ctypes.data_as(_vp) for x in cand], *[x.ctypes.data_as(_vp) for x in best], _lib.host_device(device), 0, None)
+    rc = lib.fold(int(m), n, *[_ptr(x) for x in planes], *io.tail())
     lib.check(rc, "ddf fold")
 
 
@@ -217,7 +217,6 @@ class KernelSearch:
         self._padding = self._max_shift + self._Nw + HALF             # UMPAModelDFKernel's
         if H - 2 * self._padding < 1 or W - 2 * self._padding < 1:
             raise ValueError("frames of %d x %d pixels leave no pixel inside the padding %d of the kernel model" % (H, W, self._padding))
-        from . import model
         import torch
         self._lib = _lib.ddf()
         if hasattr(sam_list[0], "data_ptr") and device is None:
@@ -244,7 +243,7 @@ class KernelSearch:
             return torch.stack([f.to(device=self._tdev, dtype=torch.float64) for f in frames]).contiguous()
         return torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f, dtype=np.float64) for f in frames]))).to(self._tdev)
 
-    # -- the kernel model's geometry (model.py: _calculate_extent, _convert_ROI_slice)
+    # -- the kernel model's geometry (model.py: _calculate_extent, resolve_region)
     @property
     def padding(self):
         return self._padding
@@ -254,21 +253,9 @@ class KernelSearch:
         return self._shape[0] - 2 * self._padding, self._shape[1] - 2 * self._padding
 
     def _region(self, ROI, step):
+        """The models' ``resolve_region`` with this class's default: without ``ROI`` the whole extent taken with ``step``."""
         N0, N1 = self.extent
-        if ROI is not None:
-            s0, s1 = ROI
-            s0 = s0.indices(N0) if type(s0) is slice else tuple(int(v) for v in s0)
-            s1 = s1.indices(N1) if type(s1) is slice else tuple(int(v) for v in s1)
-        else:
-            s0, s1 = slice(0, N0, step).indices(N0), slice(0, N1, step).indices(N1)
-        if s0[2] < 1 or s1[2] < 1:
-            raise RuntimeError('ROI steps must be positive.')
-        n0, n1 = 1 + (s0[1] - s0[0] - 1) // s0[2], 1 + (s1[1] - s1[0] - 1) // s1[2]
-        if n0 < 1 or n1 < 1:
-            raise RuntimeError('Empty ROI %s.' % ((s0, s1),))
-        if s0[0] < 0 or s1[0] < 0 or s0[0] + s0[2] * (n0 - 1) >= N0 or s1[0] + s1[2] * (n1 - 1) >= N1:
-            raise RuntimeError('ROI %s exceeds the reconstructible extent %s.' % ((s0, s1), (N0, N1)))
-        return s0, s1
+        return model.resolve_region((N0, N1), ROI, None if ROI is not None else step, ((0, N0, 1), (0, N1, 1)))[:2]
 
     def coords(self, ROI=None, step=None):
         s0, s1 = self._region(ROI, step)
@@ -324,8 +311,7 @@ class KernelSearch:
             if keep:
                 f_all[m], err_all[m] = res["f"], res["err"]
             planes = [torch.from_numpy(np.ascontiguousarray(res[k]).reshape(-1)).to(self._tdev) for k in ("f", "T", "dx", "dy", "err")]
-            rc = self._lib.fold(m, n, *[p.data_ptr() for p in planes], *[p.data_ptr() for p in best], self._device, _lib.F_DEVICE_IO, stream)
-            self._lib.check(rc, "ddf fold")
+            fold(m, planes, best)
             times["fold"] += time.perf_counter() - t2                 # the upload of the candidate's planes and the kernel
             if self.debug:                                            # the winner's debug arrays, selected on the host
                 idx = best[4].cpu().numpy().reshape(sh)

@@ -10,8 +10,6 @@ HIP only: there is no CPU fallback.
 The gauge is one global mean over the pixels that have a positive-weight edge; where zero-weight pixels cut the map into
 several connected components, every component other than the largest keeps an arbitrary constant against it.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -56,55 +54,44 @@ def _check_params(tol, maxiter):
         raise ValueError("maxiter must be a non-negative int, not %r" % (maxiter,))
 
 
-def _is_device(*arrays):
-    dev = [a is not None and hasattr(a, "data_ptr") for a in arrays]
-    given = [a is not None for a in arrays]
-    if any(dev) and dev != given:
-        raise ValueError("device arrays must be contiguous HIP tensors on one device (host arrays and tensors are not mixed)")
-    return any(dev)
+_MIXED = "device arrays must be contiguous HIP tensors on one device (host arrays and tensors are not mixed)"
 
 
-def _check_tensors(*tensors):
-    import torch
-    for t in tensors:
-        if t is None:
-            continue
-        if t.dtype != torch.float64:
-            raise ValueError("gradients and weights must be float64, not %s" % t.dtype)
-    return _lib.device_io(*tensors)
+def _typed(io, *arrays):
+    """Host arrays as contiguous float64 copies; tensors as they are, which the caller refuses with ``_refuse``."""
+    if io.on_device:
+        return arrays
+    return tuple(None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in arrays)
+
+
+def _refuse(io, *arrays):
+    """After the shapes: tensors of another dtype, host weights that are not finite and >= 0 (on tensors the library's
+    kernels define what such a weight does)."""
+    if io.on_device:
+        for t in arrays:
+            if t is not None and str(t.dtype) != "torch.float64":
+                raise ValueError("gradients and weights must be float64, not %s" % t.dtype)
+    else:
+        weight = arrays[-1]
+        if weight is not None and not (np.isfinite(weight).all() and (weight >= 0).all()):
+            raise ValueError("weights must be finite and >= 0")
 
 
 def _solve(gx, gy, weight, tol, maxiter, fill, device, flags):
     _check_params(tol, maxiter)
     lib = _lib.integrate()
-    vp = C.c_void_p
-    if _is_device(gx, gy, weight):
-        import torch
-        _check_shapes(gx.shape, gy.shape, None if weight is None else weight.shape)
-        dev, stream = _check_tensors(gx, gy, weight)
-        K = gx.shape[0] if gx.dim() == 3 else 1
-        phi = torch.empty_like(gx)
-        it, st, res = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32), np.zeros(K)
-        rc = lib.solve(gx.data_ptr(), gy.data_ptr(), weight.data_ptr() if weight is not None else None, K, gx.shape[-2], gx.shape[-1],
-                       float(tol), int(maxiter), float(fill), phi.data_ptr(), it.ctypes.data_as(vp), res.ctypes.data_as(vp),
-                       st.ctypes.data_as(vp), dev, flags | _lib.F_DEVICE_IO, stream)
-        lib.check(rc, "integrate solve")
-        single = gx.dim() == 2
-    else:
-        gx, gy = np.ascontiguousarray(gx, dtype=np.float64), np.ascontiguousarray(gy, dtype=np.float64)
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, dtype=np.float64)
-        _check_shapes(gx.shape, gy.shape, None if weight is None else weight.shape)
-        if weight is not None and not (np.isfinite(weight).all() and (weight >= 0).all()):
-            raise ValueError("weights must be finite and >= 0")
-        K = gx.shape[0] if gx.ndim == 3 else 1
-        phi = np.empty_like(gx)
-        it, st, res = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32), np.zeros(K)
-        rc = lib.solve(gx.ctypes.data_as(vp), gy.ctypes.data_as(vp), weight.ctypes.data_as(vp) if weight is not None else None,
-                       K, gx.shape[-2], gx.shape[-1], float(tol), int(maxiter), float(fill), phi.ctypes.data_as(vp),
-                       it.ctypes.data_as(vp), res.ctypes.data_as(vp), st.ctypes.data_as(vp), _lib.host_device(device), flags, None)
-        lib.check(rc, "integrate solve")
-        single = gx.ndim == 2
+    io = _lib.Side(gx, gy, weight, device=device, mixed=_MIXED)
+    gx, gy, weight = _typed(io, gx, gy, weight)
+    _check_shapes(gx.shape, gy.shape, None if weight is None else weight.shape)
+    _refuse(io, gx, gy, weight)
+    tail = io.tail(flags)
+    single = len(gx.shape) == 2
+    K = 1 if single else gx.shape[0]
+    phi = io.empty(gx.shape, np.float64)
+    it, st, res = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32), np.zeros(K)
+    rc = lib.solve(io.ptr(gx), io.ptr(gy), io.ptr(weight), K, gx.shape[-2], gx.shape[-1], float(tol), int(maxiter), float(fill),
+                   io.ptr(phi), io.ptr(it), io.ptr(res), io.ptr(st), *tail)
+    lib.check(rc, "integrate solve")
     if single:
         return Integration(phi, int(it[0]), float(res[0]), int(st[0]))
     return Integration(phi, it, res, st)
@@ -140,27 +127,14 @@ def vcycle(r, weight=None, device=None, no_tail=False, jacobi=False, diagonal=Fa
     ``diagonal=True`` returns the diagonal ``d`` of the fine operator instead (for the tests)."""
     lib = _lib.integrate()
     flags = _flags(no_tail, jacobi) | (_lib.INTEGRATE_F_DEBUG if diagonal else 0)
-    if _is_device(r, weight):
-        import torch
-        if r.dim() != 2 or (weight is not None and weight.shape != r.shape):
-            raise ValueError("r must be [H, W] and weight of the same shape")
-        dev, stream = _check_tensors(r, weight)
-        z = torch.empty_like(r)
-        rc = lib.vcycle(weight.data_ptr() if weight is not None else None, r.data_ptr(), z.data_ptr(), r.shape[0], r.shape[1],
-                        dev, flags | _lib.F_DEVICE_IO, stream)
-        lib.check(rc, "integrate vcycle")
-        return z
-    r = np.ascontiguousarray(r, dtype=np.float64)
-    if weight is not None:
-        weight = np.ascontiguousarray(weight, dtype=np.float64)
-    if r.ndim != 2 or (weight is not None and weight.shape != r.shape):
+    io = _lib.Side(r, weight, device=device, mixed=_MIXED)
+    r, weight = _typed(io, r, weight)
+    if len(r.shape) != 2 or (weight is not None and weight.shape != r.shape):
         raise ValueError("r must be [H, W] and weight of the same shape")
-    if weight is not None and not (np.isfinite(weight).all() and (weight >= 0).all()):
-        raise ValueError("weights must be finite and >= 0")
-    z = np.empty_like(r)
-    vp = C.c_void_p
-    rc = lib.vcycle(weight.ctypes.data_as(vp) if weight is not None else None, r.ctypes.data_as(vp), z.ctypes.data_as(vp),
-                    r.shape[0], r.shape[1], _lib.host_device(device), flags, None)
+    _refuse(io, r, weight)
+    tail = io.tail(flags)
+    z = io.empty(r.shape, np.float64)
+    rc = lib.vcycle(io.ptr(weight), io.ptr(r), io.ptr(z), r.shape[0], r.shape[1], *tail)
     lib.check(rc, "integrate vcycle")
     return z
 

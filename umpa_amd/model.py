@@ -78,6 +78,53 @@ def spmq(a):
     return _spfit(np.asarray(a), False)
 
 
+# -- ROI / extent arithmetic (model.pyx:531-623), as functions of the extent: the models and ddf.KernelSearch share it
+def _roi_slices(extent, ROI, step, current):
+    N0, N1 = extent
+    if ROI is not None:
+        if step is not None:
+            raise RuntimeError('Step and ROI should not be specified simultaneously.')
+        s0, s1 = ROI
+        if type(s0) is slice:
+            s0 = s0.indices(N0)
+        if type(s1) is slice:
+            s1 = s1.indices(N1)
+    else:
+        s0, s1 = current
+        if step is not None:
+            s0 = slice(s0[0], s0[1], step).indices(N0)
+            s1 = slice(s1[0], s1[1], step).indices(N1)
+    return tuple(int(v) for v in s0), tuple(int(v) for v in s1)
+
+
+def _roi_counts(s0, s1):
+    start0, end0, step0 = s0
+    start1, end1, step1 = s1
+    if step0 < 1 or step1 < 1:
+        raise RuntimeError('ROI steps must be positive.')
+    N0 = 1 + (end0 - start0 - 1) // step0                           # model.pyx:414-415
+    N1 = 1 + (end1 - start1 - 1) // step1
+    return N0, N1
+
+
+def _roi_check_range(extent, s0, s1, N0, N1):
+    E0, E1 = extent
+    if N0 < 1 or N1 < 1:
+        raise RuntimeError('Empty ROI %s.' % ((s0, s1),))
+    if s0[0] < 0 or s1[0] < 0 or s0[0] + s0[2] * (N0 - 1) >= E0 or s1[0] + s1[2] * (N1 - 1) >= E1:
+        raise RuntimeError('ROI %s exceeds the reconstructible extent %s.' % ((s0, s1), (E0, E1)))
+
+
+def resolve_region(extent, ROI, step, current):
+    """``(s0, s1, N0, N1)`` of ``ROI`` (slices or ``(start, end, step)`` triples), or of ``current`` (such triples) taken
+    with ``step``, on an image of ``extent``: the two ranges and their pixel counts.  Refused in this order: both ``ROI``
+    and ``step``, steps that are not positive, an empty region, one that leaves the extent."""
+    s0, s1 = _roi_slices(extent, ROI, step, current)
+    N0, N1 = _roi_counts(s0, s1)
+    _roi_check_range(extent, s0, s1, N0, N1)
+    return s0, s1, N0, N1
+
+
 class UMPAModelBase:
     """Mirror of ``UMPAModelBase`` (``model.pyx:116-755``)."""
 
@@ -100,7 +147,7 @@ class UMPAModelBase:
         Na = len(sam_list)
         self._handle = None
         self._lib = self._native()
-        self._device = _default_device() if device is None else int(device)
+        self._device = _lib.host_device(device)
 
         # frames and shapes (model.pyx:225-254)
         self._sam = self._prepare_frames(sam_list)
@@ -235,21 +282,7 @@ class UMPAModelBase:
         return int(N0), int(N1)
 
     def _convert_ROI_slice(self, ROI=None, step=None):
-        N0, N1 = self._calculate_extent()
-        if ROI is not None:
-            if step is not None:
-                raise RuntimeError('Step and ROI should not be specified simultaneously.')
-            s0, s1 = ROI
-            if type(s0) is slice:
-                s0 = s0.indices(N0)
-            if type(s1) is slice:
-                s1 = s1.indices(N1)
-        else:
-            s0, s1 = self._ROI
-            if step is not None:
-                s0 = slice(s0[0], s0[1], step).indices(N0)
-                s1 = slice(s1[0], s1[1], step).indices(N1)
-        return tuple(int(v) for v in s0), tuple(int(v) for v in s1)
+        return _roi_slices(self._calculate_extent(), ROI, step, self._ROI)
 
     def _set_ROI(self, ROI=None):
         N0, N1 = self._calculate_extent()
@@ -278,22 +311,17 @@ class UMPAModelBase:
     def test(self):                                                 # ModelBase::test, Model.cpp:226-234
         return float(len(self._sam))
 
-    @staticmethod
-    def _counts(s0, s1):
-        start0, end0, step0 = s0
-        start1, end1, step1 = s1
-        if step0 < 1 or step1 < 1:
-            raise RuntimeError('ROI steps must be positive.')
-        N0 = 1 + (end0 - start0 - 1) // step0                       # model.pyx:414-415
-        N1 = 1 + (end1 - start1 - 1) // step1
-        return N0, N1
+    _counts = staticmethod(_roi_counts)
 
     def _check_range(self, s0, s1, N0, N1):
-        E0, E1 = self._calculate_extent()
-        if N0 < 1 or N1 < 1:
-            raise RuntimeError('Empty ROI %s.' % ((s0, s1),))
-        if s0[0] < 0 or s1[0] < 0 or s0[0] + s0[2] * (N0 - 1) >= E0 or s1[0] + s1[2] * (N1 - 1) >= E1:
-            raise RuntimeError('ROI %s exceeds the reconstructible extent %s.' % ((s0, s1), (E0, E1)))
+        _roi_check_range(self._calculate_extent(), s0, s1, N0, N1)
+
+    def _region(self, ROI=None, step=None, ROI_wins=False):
+        """``resolve_region`` on this model: the default region is the remembered ROI.  ``ROI_wins``: ``step`` is ignored
+        beside ``ROI``, as ``match()`` ignores it, where ``coverage()`` refuses the pair."""
+        if ROI_wins and ROI is not None:
+            step = None
+        return resolve_region(self._calculate_extent(), ROI, step, self._ROI)
 
     # -- coverage (model.pyx:499-529)
     def _trivial_coverage(self):
@@ -303,9 +331,7 @@ class UMPAModelBase:
         return all(tuple(p) == (0, 0) for p in self._pos_list) and all(tuple(s) == sh0 for s in self._shape_list)
 
     def coverage(self, step=None, ROI=None):
-        s0, s1 = self._convert_ROI_slice(ROI, step)
-        N0, N1 = self._counts(s0, s1)
-        self._check_range(s0, s1, N0, N1)
+        s0, s1, N0, N1 = self._region(ROI, step)
         cmap = np.zeros((N0, N1), dtype=NPDOUBLE)
         if self._lib.is_hip:
             self._lib.check(self._lib.coverage_region(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1,
@@ -337,10 +363,8 @@ class UMPAModelBase:
         if not quiet:
             if self._lib.is_hip:
                 print("Using HIP device %d" % self._device)
-        s0, s1 = self._convert_ROI_slice(ROI, step)
-        self._set_ROI((s0, s1))
-        N0, N1 = self._counts(s0, s1)
-        self._check_range(s0, s1, N0, N1)
+        self._set_ROI(self._convert_ROI_slice(ROI, step))                # remembered before it is checked, as in the reference
+        s0, s1, N0, N1 = self._region()
         sh = (N0, N1)
         shp = (N0, N1, self.Nparam)
         planar = False
@@ -436,40 +460,25 @@ class UMPAModelBase:
         if why:
             raise RuntimeError("%s (grid search / cost volume): %s" % (what, why))
 
-    def _cost_volume(self, ROI=None, step=None, with_fit=False):
+    def _grid_cost_volume(self, ROI, step, alloc):
+        """The one ``umpa_grid_cost_volume`` call.  ``alloc(U, N0, N1)`` gives the output arrays once the model and the region
+        have passed, as a dictionary of ``cost`` and, where wanted, ``T`` and ``df``: host arrays, or HIP tensors that the
+        library fills on the current stream.  This call is given the staged stack, so it spends the one-shot flag.
+        Returns ``(s0, s1, arrays)``."""
         self._grid_check("cost_volume")
-        if (ROI is not None) and (step is not None):
-            step = None
-        s0, s1 = self._convert_ROI_slice(ROI, step)
-        N0, N1 = self._counts(s0, s1)
-        self._check_range(s0, s1, N0, N1)
-        U = 2 * self._max_shift - 1
-        out = {'cost': np.empty((U, U, N0, N1), dtype=NPDOUBLE)}
-        if with_fit:
-            out['T'] = np.empty((U, U, N0, N1), dtype=NPDOUBLE)
-            if self._kind == KIND_DF:
-                out['df'] = np.empty((U, U, N0, N1), dtype=NPDOUBLE)
-        vp = lambda k: out[k].ctypes.data if k in out else None
+        s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
+        out = alloc(2 * self._max_shift - 1, N0, N1)
+        _, flags, stream = _lib.Side(out['cost'], device=self._device).tail(self._staged_flag())
         try:
             _lib.grid().check(_lib.grid().cost_volume(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1,
-                                                      vp('cost'), vp('T'), vp('df'), self._staged_flag(), None), "grid cost_volume")
+                                                      *[_lib.Side.ptr(out.get(k)) for k in ('cost', 'T', 'df')], flags, stream), "grid cost_volume")
         except _lib.NativeError as e:
             raise RuntimeError("cost_volume: %s" % e) from None
-        return out
+        return s0, s1, out
 
-    _COST_VOLUME_DOC = """The cost of EVERY integer shift of the search box at every pixel of the region (extension; the
-        reference offers ``utils.get_cost``, a Python loop over ``cost()`` for one pixel): a dictionary with
-        ``cost[U, U, N0, N1]``, ``U = 2 max_shift - 1``, where ``cost[si + max_shift - 1, sj + max_shift - 1, xi, xj]``
-        is ``cost(i, j, si, sj)[0]`` of the region's pixel ``(xi, xj)`` (``si``: row shift, ``sj``: column shift) -- the
-        numbers ``match()`` compares, bit for bit.  ``with_fit=True`` adds ``T`` and, for the dark-field model, ``df`` in
-        the same layout.  ``ROI`` / ``step`` as for ``match()``; the model's own ROI is not changed.  A stack uploaded by
-        ``stage_sample`` and not adopted yet is adopted by this call, as by ``match()``: the volume is that stack's.
-
-        Mind the size: an array holds ``U * U * N0 * N1`` doubles -- 2.7 GB for a whole 2048 x 2048 image at
-        ``max_shift=5`` -- so a ``ROI`` of the rows or the patch in question is the normal use.
-
-        Models the plain tiled path takes whole only (no masks, no ``pos_list``, steps and search ranges within its
-        limits); anything else raises ``RuntimeError``."""
+    def _cost_volume(self, ROI=None, step=None, with_fit=False):
+        keys = ['cost'] + (['T'] + (['df'] if self._kind == KIND_DF else []) if with_fit else [])
+        return self._grid_cost_volume(ROI, step, lambda U, N0, N1: {k: np.empty((U, U, N0, N1), dtype=NPDOUBLE) for k in keys})[2]
 
     _force = 0
     _use_staged = False
@@ -658,73 +667,62 @@ class UMPAModelBase:
         return result
 
 
-class UMPAModelNoDF(UMPAModelBase):
+class _UMPAModelPlain(UMPAModelBase):
+    """What ``UMPAModelNoDF`` and ``UMPAModelDF`` share: their parameters are all outputs, ``Nparam`` of them, the last
+    ``Nparam - 2`` being what ``cost()`` returns beside the cost."""
+    safe_crop = 0
+
+    def min(self, i, j):
+        values = np.zeros((self.Nparam,), dtype=NPDOUBLE)
+        self._min(i, j, values)
+        return values
+
+    def cost(self, i, j, sx, sy):
+        """Cost, transmission and (dark-field model) dark-field at pixel (i, j) for the shift (sx rows, sy columns), rounded."""
+        values = np.zeros(self.Nparam - 2)
+        self._lib.check(self._lib.cost(self._handle, int(i), int(j), _cround(sx), _cround(sy),
+                                       _lib._ptr(values, _lib._dp)), "cost")
+        return tuple(values)
+
+    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk'):
+        """``search='walk'`` (default): the reference's minimiser.  ``search='grid'`` (extension): the global minimum over
+        all ``(2 max_shift - 1)^2`` integer shifts, then the same sub-pixel step around it (``include/umpa_grid.h``);
+        plain models only (no masks, no ``pos_list``), no ``dxdy``."""
+        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet, search=search)
+        return self._unpack(result, self._kind == KIND_DF)
+
+    def cost_volume(self, ROI=None, step=None, with_fit=False):
+        """The cost of EVERY integer shift of the search box at every pixel of the region (extension; the
+        reference offers ``utils.get_cost``, a Python loop over ``cost()`` for one pixel): a dictionary with
+        ``cost[U, U, N0, N1]``, ``U = 2 max_shift - 1``, where ``cost[si + max_shift - 1, sj + max_shift - 1, xi, xj]``
+        is ``cost(i, j, si, sj)[0]`` of the region's pixel ``(xi, xj)`` (``si``: row shift, ``sj``: column shift) -- the
+        numbers ``match()`` compares, bit for bit.  ``with_fit=True`` adds ``T`` and, for the dark-field model, ``df`` in
+        the same layout.  ``ROI`` / ``step`` as for ``match()``; the model's own ROI is not changed.  A stack uploaded by
+        ``stage_sample`` and not adopted yet is adopted by this call, as by ``match()``: the volume is that stack's.
+
+        Mind the size: an array holds ``U * U * N0 * N1`` doubles -- 2.7 GB for a whole 2048 x 2048 image at
+        ``max_shift=5`` -- so a ``ROI`` of the rows or the patch in question is the normal use.
+
+        Models the plain tiled path takes whole only (no masks, no ``pos_list``, steps and search ranges within its
+        limits); anything else raises ``RuntimeError``."""
+        return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
+
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
+        """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
+        from . import sigma
+        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step, sam=sam)
+
+
+class UMPAModelNoDF(_UMPAModelPlain):
     """Mirror of ``UMPAModelNoDF`` (``model.pyx:758-822``)."""
     Nparam = 4
-    safe_crop = 0
     _kind = KIND_NODF
 
-    def min(self, i, j):
-        values = np.zeros((self.Nparam,), dtype=NPDOUBLE)
-        self._min(i, j, values)
-        return values
 
-    def cost(self, i, j, sx, sy):
-        """Cost and transmission at pixel (i, j) for the shift (sx rows, sy columns), rounded."""
-        values = np.zeros(2)
-        self._lib.check(self._lib.cost(self._handle, int(i), int(j), _cround(sx), _cround(sy),
-                                       _lib._ptr(values, _lib._dp)), "cost")
-        return (values[0], values[1])
-
-    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk'):
-        """``search='walk'`` (default): the reference's minimiser.  ``search='grid'`` (extension): the global minimum over
-        all ``(2 max_shift - 1)^2`` integer shifts, then the same sub-pixel step around it (``include/umpa_grid.h``);
-        plain models only (no masks, no ``pos_list``), no ``dxdy``."""
-        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet, search=search)
-        return self._unpack(result, False)
-
-    def cost_volume(self, ROI=None, step=None, with_fit=False):
-        return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
-    cost_volume.__doc__ = UMPAModelBase._COST_VOLUME_DOC
-
-    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
-        """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
-        from . import sigma
-        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step, sam=sam)
-
-
-class UMPAModelDF(UMPAModelBase):
+class UMPAModelDF(_UMPAModelPlain):
     """Mirror of ``UMPAModelDF`` (``model.pyx:824-896``)."""
     Nparam = 5
-    safe_crop = 0
     _kind = KIND_DF
-
-    def min(self, i, j):
-        values = np.zeros((self.Nparam,), dtype=NPDOUBLE)
-        self._min(i, j, values)
-        return values
-
-    def cost(self, i, j, sx, sy):
-        values = np.zeros(3)
-        self._lib.check(self._lib.cost(self._handle, int(i), int(j), _cround(sx), _cround(sy),
-                                       _lib._ptr(values, _lib._dp)), "cost")
-        return (values[0], values[1], values[2])
-
-    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk'):
-        """``search='walk'`` (default): the reference's minimiser.  ``search='grid'`` (extension): the global minimum over
-        all ``(2 max_shift - 1)^2`` integer shifts, then the same sub-pixel step around it (``include/umpa_grid.h``);
-        plain models only (no masks, no ``pos_list``), no ``dxdy``."""
-        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet, search=search)
-        return self._unpack(result, True)
-
-    def cost_volume(self, ROI=None, step=None, with_fit=False):
-        return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
-    cost_volume.__doc__ = UMPAModelBase._COST_VOLUME_DOC
-
-    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
-        """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
-        from . import sigma
-        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step, sam=sam)
 
     @property
     def Im(self):

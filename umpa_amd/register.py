@@ -13,8 +13,6 @@ overlapping part of the frames only (``boundary='overlap'``).  Everything after 
 Left out: ``find_shift`` and ``get_new_diff_pos`` (speckle tracking with a large window: ``UMPA_normal`` plus
 ``solve_positions`` below express it), the reference's tuple-of-two-masks form of ``w``, ``numiter > 1``, plotting.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -67,39 +65,33 @@ def shift_sums(a, b, w=None, max_shift=8, boundary="wrap", device=None):
     S = _box(max_shift)
     lib = _lib.register()
     U = (2 * S[0] + 1, 2 * S[1] + 1)
-    if hasattr(b, "data_ptr"):
+    io = _lib.Side(b, a, w, device=device)
+    if io.on_device:
         import torch
         code = {torch.float64: 0, torch.float32: 1, getattr(torch, "uint16", None): 2}.get(b.dtype)
         if code is None or a.dtype != b.dtype or (w is not None and w.dtype != torch.float64):
             raise ValueError("frames must be float64, float32 or uint16 (a and b alike), weights float64.")
-        _check_shapes(a.shape, b.shape, None if w is None else w.shape, S)
-        dev, stream = _lib.device_io(b, a, w)
-        K = b.shape[0] if b.dim() == 3 else 1
-        out = torch.empty((3, K) + U, dtype=torch.float64, device=b.device)
-        flags = _lib.F_DEVICE_IO | (_lib.REGISTER_F_SHARED_A if a.dim() == 2 else 0) | (_lib.REGISTER_F_SHARED_W if w is not None and w.dim() == 2 else 0)
-        rc = lib.sums(a.data_ptr(), b.data_ptr(), w.data_ptr() if w is not None else None, code, K, b.shape[-2], b.shape[-1],
-                      S[0], S[1], BOUNDARY[boundary], out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), dev, flags, stream)
-        lib.check(rc, "register sums")
-        return tuple(out[i] if b.dim() == 3 else out[i, 0] for i in range(3))
-    a, b = np.asarray(a), np.asarray(b)
-    code = _CODE.get(b.dtype)
-    if code is None or a.dtype != b.dtype:
-        raise ValueError("frames must be float64, float32 or uint16 (a and b alike), not %s and %s." % (a.dtype, b.dtype))
-    if w is not None:
-        w = np.ascontiguousarray(w, dtype=np.float64)
+    else:
+        a, b = np.asarray(a), np.asarray(b)
+        code = _CODE.get(b.dtype)
+        if code is None or a.dtype != b.dtype:
+            raise ValueError("frames must be float64, float32 or uint16 (a and b alike), not %s and %s." % (a.dtype, b.dtype))
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
     _check_shapes(a.shape, b.shape, None if w is None else w.shape, S)
-    if w is not None and not (np.isfinite(w).all() and (w >= 0).all()):
-        raise ValueError("weights must be finite and >= 0")
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    K = b.shape[0] if b.ndim == 3 else 1
-    out = np.empty((3, K) + U, dtype=np.float64)
-    flags = (_lib.REGISTER_F_SHARED_A if a.ndim == 2 else 0) | (_lib.REGISTER_F_SHARED_W if w is not None and w.ndim == 2 else 0)
-    vp = C.c_void_p
-    rc = lib.sums(a.ctypes.data_as(vp), b.ctypes.data_as(vp), w.ctypes.data_as(vp) if w is not None else None, code, K,
-                  b.shape[-2], b.shape[-1], S[0], S[1], BOUNDARY[boundary],
-                  out[0].ctypes.data_as(vp), out[1].ctypes.data_as(vp), out[2].ctypes.data_as(vp), _lib.host_device(device), flags, None)
+    if not io.on_device:                                              # (on tensors the kernels define what a bad weight does)
+        if w is not None and not (np.isfinite(w).all() and (w >= 0).all()):
+            raise ValueError("weights must be finite and >= 0")
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    shared = (_lib.REGISTER_F_SHARED_A if len(a.shape) == 2 else 0) | (_lib.REGISTER_F_SHARED_W if w is not None and len(w.shape) == 2 else 0)
+    tail = io.tail(shared)
+    batch = len(b.shape) == 3
+    K = b.shape[0] if batch else 1
+    out = io.empty((3, K) + U, np.float64)
+    rc = lib.sums(io.ptr(a), io.ptr(b), io.ptr(w), code, K, b.shape[-2], b.shape[-1], S[0], S[1], BOUNDARY[boundary],
+                  io.ptr(out[0]), io.ptr(out[1]), io.ptr(out[2]), *tail)
     lib.check(rc, "register sums")
-    return tuple(out[i] if b.ndim == 3 else out[i, 0] for i in range(3))
+    return tuple(out[i] if batch else out[i, 0] for i in range(3))
 
 
 def _host(t):
@@ -327,9 +319,7 @@ def shift_data(frames, shift_list, interp="cubic", device=None):
     shifts = np.asarray(shift_list, dtype=np.float64).reshape(-1, 2)
     if frames.ndim != 3 or len(shifts) != len(frames):
         raise ValueError("frames must be [K, H, W] with one (row, col) shift per frame, not %r and %r" % (frames.shape, shifts.shape))
-    if device is None:
-        from . import model
-        device = model._default_device()
+    device = _lib.host_device(device)
     out = np.empty(frames.shape, dtype=np.float64)
     d0, d1 = np.empty(frames.shape[1:], np.float32), np.empty(frames.shape[1:], np.float32)
     for k in range(len(frames)):

@@ -8,8 +8,6 @@ integer shift -- in the sandwich form, because the window weights are not invers
 the residual after a linearised sub-pixel refit.  ``Uncertainty.weight()`` is an inverse-variance weight for
 ``phase_from_match(result, weight=...)``.  HIP only: there is no CPU fallback.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -48,11 +46,8 @@ def region(sam, ref, win, max_shift, kind, area, shift, moments=False, device=No
     if N0 < 1 or N1 < 1:
         raise ValueError("an empty region: %d x %d pixels" % (N0, N1))
     lib = _lib.sigma()
-    vp = C.c_void_p
-    on_device = hasattr(sam, "data_ptr")
-    if on_device != hasattr(ref, "data_ptr") or on_device != hasattr(shift, "data_ptr"):
-        raise ValueError("sam, ref and shift must all be host arrays or all HIP tensors")
-    if on_device:
+    io = _lib.Side(sam, ref, shift, device=device, mixed="sam, ref and shift must all be host arrays or all HIP tensors")
+    if io.on_device:
         import torch
         if sam.dtype != torch.float64 or ref.dtype != torch.float64 or shift.dtype != torch.int32:
             raise ValueError("sam and ref must be float64 and shift int32")
@@ -64,23 +59,20 @@ def region(sam, ref, win, max_shift, kind, area, shift, moments=False, device=No
     if tuple(shift.shape) != (2, N0, N1):
         raise ValueError("shift must be [2, %d, %d], not %r" % (N0, N1, tuple(shift.shape)))
     K, H, W = (int(v) for v in sam.shape)
-    shapes = {"unit": (3, N0, N1), "s2": (N0, N1), "dof": (N0, N1), "valid": (N0, N1)}
-    if moments:
-        shapes["moments"] = (P, N0, N1)
-    if on_device:
-        dev, stream = _lib.device_io(sam, ref, shift)
-        out = {k: torch.empty(s, dtype=torch.int32 if k == "valid" else torch.float64, device=sam.device) for k, s in shapes.items()}
-        ptr = lambda k: out[k].data_ptr() if k in out else None
-        rc = lib.region(sam.data_ptr(), ref.data_ptr(), K, H, W, win.ctypes.data_as(vp), Nw, int(max_shift), kind,
-                        start0, step0, N0, start1, step1, N1, shift.data_ptr(), ptr("moments"), ptr("unit"), ptr("s2"),
-                        ptr("dof"), ptr("valid"), dev, _lib.F_DEVICE_IO, stream)
-    else:
-        out = {k: np.empty(s, dtype=np.int32 if k == "valid" else np.float64) for k, s in shapes.items()}
-        ptr = lambda k: out[k].ctypes.data_as(vp) if k in out else None
-        rc = lib.region(sam.ctypes.data_as(vp), ref.ctypes.data_as(vp), K, H, W, win.ctypes.data_as(vp), Nw, int(max_shift), kind,
-                        start0, step0, N0, start1, step1, N1, shift.ctypes.data_as(vp), ptr("moments"), ptr("unit"), ptr("s2"),
-                        ptr("dof"), ptr("valid"), _lib.host_device(device), 0, None)
+    tail = io.tail()
+    out = _outputs(io, (N0, N1), (P, N0, N1) if moments else None)
+    rc = lib.region(io.ptr(sam), io.ptr(ref), K, H, W, io.ptr(win), Nw, int(max_shift), kind, start0, step0, N0, start1, step1, N1,
+                    io.ptr(shift), *[io.ptr(out.get(k)) for k in ("moments", "unit", "s2", "dof", "valid")], *tail)
     lib.check(rc, "sigma region")
+    return out
+
+
+def _outputs(io, sh, moments=None):
+    """The result dictionary of both stages for planes of the shape ``sh``, on the side of ``io``."""
+    out = {"unit": io.empty((3,) + sh, np.float64), "s2": io.empty(sh, np.float64), "dof": io.empty(sh, np.float64),
+           "valid": io.empty(sh, np.int32)}
+    if moments:
+        out["moments"] = io.empty(moments, np.float64)
     return out
 
 
@@ -89,29 +81,20 @@ def solve(moments, kind, K, sv, device=None):
     ``unit`` (``[3, ...]``), ``s2``, ``dof`` and ``valid`` in the shape of one plane."""
     P = _planes(kind)
     lib = _lib.sigma()
-    vp = C.c_void_p
     if tuple(moments.shape)[:1] != (P,) or len(moments.shape) < 2:
         raise ValueError("moments must be [%d, ...] for kind %d, not %r" % (P, kind, tuple(moments.shape)))
     sh = tuple(int(v) for v in moments.shape[1:])
     n = int(np.prod(sh))
     if n < 1:
         raise ValueError("moments of %r: no pixel" % (tuple(moments.shape),))
-    if hasattr(moments, "data_ptr"):
-        import torch
-        if moments.dtype != torch.float64:
-            raise ValueError("moments must be float64, not %s" % moments.dtype)
-        dev, stream = _lib.device_io(moments)
-        out = {"unit": torch.empty((3,) + sh, dtype=torch.float64, device=moments.device)}
-        for k in ("s2", "dof"):
-            out[k] = torch.empty(sh, dtype=torch.float64, device=moments.device)
-        out["valid"] = torch.empty(sh, dtype=torch.int32, device=moments.device)
-        rc = lib.solve(moments.data_ptr(), kind, int(K), n, float(sv), out["unit"].data_ptr(), out["s2"].data_ptr(),
-                       out["dof"].data_ptr(), out["valid"].data_ptr(), dev, _lib.F_DEVICE_IO, stream)
-    else:
+    io = _lib.Side(moments, device=device)
+    if not io.on_device:
         moments = np.ascontiguousarray(moments, dtype=np.float64)
-        out = {"unit": np.empty((3,) + sh), "s2": np.empty(sh), "dof": np.empty(sh), "valid": np.empty(sh, dtype=np.int32)}
-        rc = lib.solve(moments.ctypes.data_as(vp), kind, int(K), n, float(sv), *[out[k].ctypes.data_as(vp) for k in ("unit", "s2", "dof", "valid")],
-                       _lib.host_device(device), 0, None)
+    elif str(moments.dtype) != "torch.float64":
+        raise ValueError("moments must be float64, not %s" % moments.dtype)
+    tail = io.tail()
+    out = _outputs(io, sh)
+    rc = lib.solve(io.ptr(moments), kind, int(K), n, float(sv), *[io.ptr(out[k]) for k in ("unit", "s2", "dof", "valid")], *tail)
     lib.check(rc, "sigma solve")
     return out
 
@@ -230,11 +213,7 @@ def uncertainty(model, result, noise_var=None, ROI=None, step=None, sam=None):
     _check_model(model)
     if noise_var is not None and not (np.isfinite(noise_var) and noise_var >= 0 and np.ndim(noise_var) == 0):
         raise ValueError("noise_var must be a finite scalar >= 0, not %r" % (noise_var,))
-    if (ROI is not None) and (step is not None):
-        step = None
-    s0, s1 = model._convert_ROI_slice(ROI, step)
-    N0, N1 = model._counts(s0, s1)
-    model._check_range(s0, s1, N0, N1)
+    s0, s1, N0, N1 = model._region(ROI, step, ROI_wins=True)
     if tuple(np.shape(result["dx"])) != (N0, N1):
         raise ValueError("the maps of result are %r, the region has %d x %d pixels" % (tuple(np.shape(result["dx"])), N0, N1))
     if sam is not None:

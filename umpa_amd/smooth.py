@@ -9,8 +9,6 @@ changes between neighbours, then the minimum is taken.  ``match_smooth`` uses th
 per-pixel start shift of the ordinary walk: regularisation chooses the basin, the data term alone gives ``dx``, ``dy``,
 ``T``, ``df`` and ``f``.  HIP only: there is no CPU fallback.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -70,31 +68,18 @@ def aggregate(cost, lam, trunc, paths=8, return_total=False, device=None, dirs=N
     if not 1 <= mask <= _lib.SMOOTH_ALL_DIRS:
         raise ValueError("dirs must be a mask of the directions 0 to 7, not %r" % (dirs,))
     lib = _lib.smooth()
-    vp = C.c_void_p
-    if hasattr(cost, "data_ptr"):
-        import torch
-        if cost.dtype != torch.float64:
-            raise ValueError("cost must be float64, not %s" % cost.dtype)
-        U, N0, N1 = _volume_shape(cost.shape)
-        dev, stream = _lib.device_io(cost)
-        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=cost.device)
-        out = {"shift": mk((2, N0, N1), torch.int32), "smin": mk((N0, N1), torch.float64),
-               "margin": mk((N0, N1), torch.float64), "valid": mk((N0, N1), torch.int32)}
-        if return_total:
-            out["total"] = mk(tuple(cost.shape), torch.float64)
-        ptr = lambda k: out[k].data_ptr() if k in out else None
-        rc = lib.aggregate(cost.data_ptr(), U, N0, N1, lam, trunc, mask, ptr("shift"), ptr("smin"), ptr("margin"), ptr("valid"),
-                           ptr("total"), dev, _lib.F_DEVICE_IO, stream)
-    else:
+    io = _lib.Side(cost, device=device)
+    if not io.on_device:
         cost = np.ascontiguousarray(cost, dtype=np.float64)
-        U, N0, N1 = _volume_shape(cost.shape)
-        out = {"shift": np.empty((2, N0, N1), dtype=np.int32), "smin": np.empty((N0, N1)),
-               "margin": np.empty((N0, N1)), "valid": np.empty((N0, N1), dtype=np.int32)}
-        if return_total:
-            out["total"] = np.empty(cost.shape)
-        ptr = lambda k: out[k].ctypes.data_as(vp) if k in out else None
-        rc = lib.aggregate(cost.ctypes.data_as(vp), U, N0, N1, lam, trunc, mask, ptr("shift"), ptr("smin"), ptr("margin"),
-                           ptr("valid"), ptr("total"), _lib.host_device(device), 0, None)
+    elif str(cost.dtype) != "torch.float64":
+        raise ValueError("cost must be float64, not %s" % cost.dtype)
+    U, N0, N1 = _volume_shape(cost.shape)
+    tail = io.tail()
+    out = {"shift": io.empty((2, N0, N1), np.int32), "smin": io.empty((N0, N1), np.float64),
+           "margin": io.empty((N0, N1), np.float64), "valid": io.empty((N0, N1), np.int32)}
+    if return_total:
+        out["total"] = io.empty(cost.shape, np.float64)
+    rc = lib.aggregate(io.ptr(cost), U, N0, N1, lam, trunc, mask, *[io.ptr(out.get(k)) for k in ("shift", "smin", "margin", "valid", "total")], *tail)
     lib.check(rc, "smooth aggregate")
     return out
 
@@ -142,24 +127,16 @@ def match_smooth(model, lam=None, trunc=None, paths=8, ROI=None, step=None, quie
     raises what ``cost_volume()`` raises.  Mind the memory: four volumes of ``(2 max_shift - 1)^2 N0 N1`` doubles."""
     import torch
     _dirs(paths)
-    model._grid_check("cost_volume")
-    if (ROI is not None) and (step is not None):
-        step = None
-    s0, s1 = model._convert_ROI_slice(ROI, step)
-    N0, N1 = model._counts(s0, s1)
-    model._check_range(s0, s1, N0, N1)
-    U = 2 * model._max_shift - 1
-    if not _lib.SMOOTH_MIN_U <= U <= _lib.SMOOTH_MAX_U:
-        raise RuntimeError("match_smooth: max_shift = %d (2 to 8 are supported)" % model._max_shift)
     dev = torch.device("cuda", model._device)
+
+    def volume(U, N0, N1):
+        if not _lib.SMOOTH_MIN_U <= U <= _lib.SMOOTH_MAX_U:
+            raise RuntimeError("match_smooth: max_shift = %d (2 to 8 are supported)" % model._max_shift)
+        return {"cost": torch.empty((U, U, N0, N1), dtype=torch.float64, device=dev)}
+
+    s0, s1, out = model._grid_cost_volume(ROI, step, volume)
     with torch.cuda.device(dev):
-        cost = torch.empty((U, U, N0, N1), dtype=torch.float64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        try:
-            _lib.grid().check(_lib.grid().cost_volume(model._handle, s0[0], s0[2], N0, s1[0], s1[2], N1, cost.data_ptr(), None, None,
-                                                      _lib.F_DEVICE_IO | model._staged_flag(), stream), "grid cost_volume")
-        except _lib.NativeError as e:
-            raise RuntimeError("cost_volume: %s" % e) from None
+        cost = out.pop("cost")
         if lam is None or trunc is None:
             unit = cost_scale(cost)
             lam = LAM_REL * unit if lam is None else lam
