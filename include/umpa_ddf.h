@@ -41,6 +41,11 @@
  * The comparison is a strict <: of equal costs the first stays, and a NaN cost never replaces anything.  A search over a
  * single candidate returns that candidate's match untouched.
  *
+ * The fold ranks by whatever the caller passes as f, so f must be a COST.  The plain match's f is one with sub-pixel modes
+ * -1 and 1 (the fitted minimum).  With sub_pixel_mode 0 it is the start offset 1 - ip of the reference, 0 or 1: a search in
+ * that mode passes the cost at the candidate's integer minimum instead, the centre dbg_d[12] of the match's 5 x 5 memo
+ * (umpa_amd/ddf.py does, and returns that cost as f).
+ *
  * Link libumpa_ddf.so and libumpa_hip.so.  Error text of every call here: umpa_ddf_last_error().
  */
 #ifndef UMPA_DDF_H

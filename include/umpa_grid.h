@@ -36,6 +36,20 @@ extern "C" {
  *   err = 0 where that 4x4 neighbourhood leaves the search range: dx, dy are the integer minimum, f its cost, T (df) its
  *     fit; dbg_a is zero;
  *   err = 0 and zeros (dbg_d: -1) where no shift has a finite cost.
+ *
+ * Non-finite costs (a NaN or an Inf pixel inside a window makes the costs of that window NaN; tests/consumer_expect.py
+ * has the footprint).  Every comparison above is a plain `<` of doubles, and nothing else looks at a cost:
+ *   the minimum: a shift wins iff its cost is `<` the best so far, which starts at +Inf.  NaN and +Inf never win.  -Inf
+ *   is a cost like any other: the first -Inf shift wins and stays (no input of the tests produces one; Inf pixels give
+ *   NaN costs, Inf - Inf);
+ *   "no shift has a finite cost" means: no cost is < +Inf.  Such a pixel has err = 0, f = T = dx = dy (= df) = 0, dbg_a
+ *   zero, every dbg_d cell -1 and dbg_ncalls = (2 max_shift - 1)^2 like every other pixel: the count is of the shifts
+ *   looked at, not of the finite ones;
+ *   a pixel with a finite minimum but a NaN among the 5x5 cells around it: the quadrant tests `cost(+1) < cost(-1)` are
+ *   false on a NaN (ip, jp = 0), the 4x4 neighbourhood and the sub-pixel fit are evaluated on the cells as they are, so
+ *   err is 0 or 1 by the range rule alone and dx, dy, f of an err = 1 pixel may be NaN with sub-pixel modes -1 and 1;
+ *   dbg_d and dbg_a hold the cells, NaN included.  T (df) stay the integer minimum's.  Callers that need
+ *   finite maps test them (umpa_amd.sigma.shift_field does).
  */
 int umpa_grid_match_region(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
                            double *values, int nparam, double *uv, int *err,

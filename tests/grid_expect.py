@@ -70,14 +70,15 @@ def near_tie(cost, bound):
     return (c2[1] - c2[0]) < (b2[0] + b2[1])
 
 
-def expected(kind, sam, ref, win, ms, pad, assign, subpx):
+def expected(kind, sam, ref, win, ms, pad, assign, subpx, volumes=None):
     """(maps, near-tie mask): maps = dict of err, debug_Ncalls, dx, dy, f, T, (df,) debug_a, debug_d, plus `ci`, `cj` (the
-    integer minimum) and `cmin` / `cmin_bound` (its extended-precision cost and fp64 bound)."""
+    integer minimum) and `cmin` / `cmin_bound` (its extended-precision cost and fp64 bound).  `volumes`: what hp_volumes
+    returned for these arguments, where the caller has it already."""
     from oracle import cpu_model
     import ctypes as C
     lib = cpu_model.native("port")
     dp = C.POINTER(C.c_double)
-    v = hp_volumes(kind, sam, ref, win, ms, pad, assign)
+    v = hp_volumes(kind, sam, ref, win, ms, pad, assign) if volumes is None else volumes
     cost, bound = v["cost"], v["bound"]
     U = 2 * ms - 1
     N0, N1 = cost.shape[2:]

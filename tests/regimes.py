@@ -8,6 +8,9 @@ large mean (where the expanded cost sums cancel), negative values, and NaN / Inf
 
 CONFIGS names the matching paths of the library, one model configuration each; `run` builds and matches one of them on
 either namespace (umpa_amd.model or the CPU oracle's), so that the CPU module judges exactly the cases the GPU module runs.
+
+tests/consumer_expect.py takes the generators, BAD_VALUES and bad_positions from here for the consumers of the shift table
+besides the walk (grid search, cost volume, aggregation, uncertainty, kernel search).
 """
 import numpy as np
 

@@ -138,10 +138,12 @@ def _ldl_solve(L, D, b):
     return x
 
 
-def solve(mom, kind, K, sv):
-    """MODEL and SOLVE of the header on [P, ...] float64 moments, expression by expression: a dictionary with unit
-    ([3, ...]), s2, dof (float64) and valid (int32)."""
-    m = np.asarray(mom, dtype=np.float64)
+def solve(mom, kind, K, sv, dtype=np.float64):
+    """MODEL and SOLVE of the header on [P, ...] moments, expression by expression, in `dtype` (float64: the header's
+    arithmetic; np.longdouble: the same source text as the yardstick of tests/consumer_expect.py -- every constant below is a
+    small integer or `sv`, a double, so the array's type decides the precision of every operation): a dictionary with unit
+    ([3, ...]), s2, dof (`dtype`) and valid (int32)."""
+    m = np.asarray(mom, dtype=dtype)
     assert m.shape[0] == PLANES[kind]
     n = 4 if kind else 3
     A = [[None] * n for _ in range(n)]

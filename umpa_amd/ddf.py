@@ -195,7 +195,14 @@ class KernelSearch:
     winner's ``a``, ``b``, ``c``, ``sigma_major``, ``sigma_minor``, ``theta`` (NaN where ``index < 0``) and its ``f``, ``T``,
     ``dx``, ``dy``, ``err``; extent, ROI / step semantics and coordinates are those of ``UMPAModelDFKernel`` on the same
     stacks, so ``np.stack([a, b, c], -1)`` can go into ``UMPAModelDFKernel.match(abc=...)``.  Pixels where all candidates
-    failed keep the first candidate's maps.  ``last_times`` holds the host-clock seconds the last ``match`` spent in
+    failed keep the first candidate's maps.
+
+    The candidates are ranked by ``f``, the cost the sub-pixel fit returns (``sub_pixel_mode`` -1 and 1).  With
+    ``sub_pixel_mode = 0`` the plain model's ``f`` is the start offset ``1 - ip`` of the reference, 0 or 1, and no cost: the
+    search then asks the plain model for its 5 x 5 memo, ranks the candidates by the memo's centre (``debug_d[..., 12]``, the
+    cost at the candidate's own integer minimum) and returns that cost as ``f`` and ``f_all``.
+
+    ``last_times`` holds the host-clock seconds the last ``match`` spent in
     the blurs, the plain matches and the folds."""
 
     def __init__(self, sam_list, ref_list, window_size=2, max_shift=4, device=None, mask_list=None, pos_list=None):
@@ -287,7 +294,10 @@ class KernelSearch:
         s0, s1 = self._region(ROI, step)
         roi = ((s0[0] + HALF, s0[1] + HALF, s0[2]), (s1[0] + HALF, s1[1] + HALF, s1[2]))   # the plain model's pixels
         M = len(cand)
-        self._model.debug = self.debug
+        # mode 0: the plain model's f is the start offset 1 - ip, no cost; the cost of the integer minimum is the centre
+        # of the 5 x 5 memo, so the plain model is asked for the memo whatever `debug` says
+        mode0 = self.sub_pixel_mode == 0
+        self._model.debug = True if mode0 and (not self.debug or self.debug == "ncalls") else self.debug
         stream = torch.cuda.current_stream(self._tdev).cuda_stream
         best = None
         f_all = err_all = None
@@ -308,14 +318,16 @@ class KernelSearch:
                        [torch.empty(n, dtype=torch.int32, device=self._tdev) for _ in range(2)]
                 if keep:
                     f_all, err_all = np.empty((M,) + sh), np.empty((M,) + sh, dtype=np.int32)
+            cost = np.ascontiguousarray(res["debug_d"][..., 12]) if mode0 else res["f"]
             if keep:
-                f_all[m], err_all[m] = res["f"], res["err"]
-            planes = [torch.from_numpy(np.ascontiguousarray(res[k]).reshape(-1)).to(self._tdev) for k in ("f", "T", "dx", "dy", "err")]
+                f_all[m], err_all[m] = cost, res["err"]
+            planes = [torch.from_numpy(np.ascontiguousarray(x).reshape(-1)).to(self._tdev)
+                      for x in (cost, res["T"], res["dx"], res["dy"], res["err"])]
             fold(m, planes, best)
             times["fold"] += time.perf_counter() - t2                 # the upload of the candidate's planes and the kernel
             if self.debug:                                            # the winner's debug arrays, selected on the host
                 idx = best[4].cpu().numpy().reshape(sh)
-                for k in ("debug_d", "debug_a", "debug_Ncalls"):
+                for k in ("debug_Ncalls",) if self.debug == "ncalls" else ("debug_d", "debug_a", "debug_Ncalls"):
                     if k in res:
                         if m == 0:
                             dbg[k] = np.array(res[k])
