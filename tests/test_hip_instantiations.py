@@ -269,6 +269,24 @@ def test_corr_march_plans(hip_ns, port_ns, monkeypatch, Nw, ms, K, df):
         np.testing.assert_allclose(got["T"][ok], vol["T"][ok], rtol=1e-9)
 
 
+def test_corr_march_ignores_the_on_demand_switch(hip_ns, monkeypatch):
+    """corr_march always computes its whole table: UMPA_HIP_ONDEMAND unset, 0 and 1 give the same maps bit for bit, launch the
+    same kernels the same number of times, and last_stats reports the exhaustive table, nothing parked, no tile missed."""
+    Nw, ms, K = 6, 5, 4
+    pad = Nw + ms
+    sam, ref = _stack(60 + 2 * pad, 80 + 2 * pad, K, ms, True, 117, 3.0)
+    runs = {}
+    for od in (None, "0", "1"):
+        env = {"UMPA_HIP_CORR_SHAPE": None, "UMPA_HIP_MARCH": None, "UMPA_HIP_ONDEMAND": od}
+        got, path, fam, st = _hip_match(hip_ns, "UMPAModelDF", sam, ref, Nw, ms, env=env, monkeypatch=monkeypatch)
+        assert path == 2 and fam.get("corr_march", 0) >= 1 and fam.get("replay_walk", 0) >= 1 and "corr_volume" not in fam, (od, path, fam)
+        assert st[1] > 0 and st[0] == st[1] and st[2] == 0 and st[3] == 0, (od, st)
+        runs[od] = (got, fam)
+    for od in ("0", "1"):
+        _same(runs[od][0], runs[None][0], "UMPA_HIP_ONDEMAND=%s against unset" % od)
+        assert runs[od][1] == runs[None][1], (od, runs[od][1], runs[None][1])
+
+
 # ----------------------------------------------------------------------------- 4. the search-range edge of the tiled path
 
 @pytest.mark.parametrize("ms", [17, 18])

@@ -136,7 +136,8 @@ def test_power_of_two_scales_change_no_bit(ns, name):
 # ----------------------------------------------------------------------------- c. on-demand passes
 
 # (the shapes of test_on_demand_table_passes_change_nothing, where units are left out and walks are parked at scale 1)
-OD_CFG = {"volume": dict(H=420, W=520, K=4, Nw=3, ms=6, amp=4.5), "march": dict(H=420, W=520, K=4, Nw=7, ms=8, amp=6.0, march_rows=64)}
+# ("masked": with that test's mask -- the scheme is on by default for models with masks)
+OD_CFG = {"volume": dict(H=420, W=520, K=4, Nw=3, ms=6, amp=4.5), "masked": dict(H=330, W=400, K=4, Nw=4, ms=5, amp=3.5, mask=True)}
 OD_REGIMES = {"x2^16": lambda s, r: R.scaled(s, r, 16, 16), "tie": lambda s, r: R.tie_scaled(s, r, -9, 1.0),
               "vis1e-2": lambda s, r: R.counts(s, r, 40000, 1e-2)}
 
@@ -151,12 +152,11 @@ def test_on_demand_passes_change_nothing_at_other_scales(ns, monkeypatch, kernel
     c = OD_CFG[kernel]
     sam, ref, _ = make_stack(c["H"], c["W"], c["K"], c["ms"], df=True, seed=31, amplitude=c["amp"], order=1)
     sam, ref = OD_REGIMES[regime](sam, ref)
-    if "march_rows" in c:
-        monkeypatch.setenv("UMPA_HIP_MARCH_OD_ROWS", str(c["march_rows"]))
+    mask = (np.random.default_rng(2).random(sam.shape) < 0.93).astype(np.float64) if c.get("mask") else None
     out, stats = {}, {}
     for od in ("0", "1"):
         monkeypatch.setenv("UMPA_HIP_ONDEMAND", od)
-        m = ns[0].UMPAModelDF(sam, ref, window_size=c["Nw"], max_shift=c["ms"])
+        m = ns[0].UMPAModelDF(sam, ref, mask_list=mask, window_size=c["Nw"], max_shift=c["ms"])
         m._force = _lib.F_FORCE_TILED
         out[od] = m.match(quiet=True)
         assert m._lib.last_path(m._handle) == 2

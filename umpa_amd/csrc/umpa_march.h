@@ -50,7 +50,7 @@ struct MarchArgs {
     int N1;
     int sigma;                // +1: B = ref sits at p+u ('sam' mode); -1: B = sam sits at p-u ('ref' mode)
     int br0, br1, bc0, bc1, Wf;   // image rows / columns inside every frame, the frames' common width
-    int nstrips, nbands, band_rows, npass, nuy;
+    int nstrips, nbands, band_rows, npass, nuy;   // nbands, band_rows: picked by launch_march (umpa_tiled.h)
     int npa, npb;             // LDS-DMA instructions per step: A pieces (64 per frame: whole instructions), B pieces (36+ per frame)
     unsigned a_slot, b_slot;  // bytes of one A / B row slot (b_slot a multiple of 256)
     int da, db;               // ring depths (rows): LA + 1, nuy + LA
@@ -58,16 +58,6 @@ struct MarchArgs {
     const char* baseB;
     unsigned frame_off[2 * UMPA_MARCH_KMAX];   // [2][Na]: byte offset of frame k's image origin (position folded in) from baseA / baseB
     int ablate;               // diagnostics: 1 no DMA, 2 no frame loop, 4 no filters, 8 no stores
-    // which (strip, band, pass) units the launch computes (on-demand passes, umpa_ondemand.h: a unit = a "tile" lin = band *
-    // nstrips + strip and a pass):
-    //   items == nullptr: the static grid, every (strip, band) x every pass;
-    //   items != nullptr: the work list ((lin << 8) | pass), *nitems entries; the grid has a slot for every unit there could be
-    //   and the workgroups past the list's end leave at once.
-    // done / ndone (or null): the unit's bit is set in done[lin] and *ndone counted when its planes are written (read by later launches).
-    const int* items;
-    const int* nitems;
-    unsigned long long* done;
-    int* ndone;
 };
 
 template <int NW, int NXB>
@@ -121,19 +111,10 @@ corr_march_kernel(ModelDev m, MarchArgs A, Sep1D sep)
     const int tid = threadIdx.x;
     const int ms = m.ms, UJ = 2 * ms - 1, K = m.Na;
     // ---- (strip, band, pass) of this workgroup: the passes of one (strip, band) on consecutive slots of one XCD
-    int item, pass;
-    if (A.items) {                                                    // the list cut into 8 contiguous ranges, one per XCD
-        const int n = __builtin_amdgcn_readfirstlane(gp(A.nitems)[0]), per_xcd = (n + 7) >> 3;
-        const int seq = blockIdx.x >> 3, idx = (blockIdx.x & 7) * per_xcd + seq;
-        if (seq >= per_xcd || idx >= n) return;
-        const int it = __builtin_amdgcn_readfirstlane(gp(A.items)[idx]);
-        item = it >> 8; pass = it & 255;
-    } else {
-        const int nitems = A.nstrips * A.nbands, per_xcd = (nitems + 7) >> 3;
-        const int seq = blockIdx.x >> 3;
-        item = (blockIdx.x & 7) * per_xcd + seq / A.npass; pass = seq % A.npass;   // (items to the XCDs in turn instead: no difference, C3 26.6 / 26.3 ms)
-        if (seq / A.npass >= per_xcd || item >= nitems) return;
-    }
+    const int nitems = A.nstrips * A.nbands, per_xcd = (nitems + 7) >> 3;
+    const int seq = blockIdx.x >> 3;
+    const int item = (blockIdx.x & 7) * per_xcd + seq / A.npass, pass = seq % A.npass;   // (items to the XCDs in turn instead: no difference, C3 26.6 / 26.3 ms)
+    if (seq / A.npass >= per_xcd || item >= nitems) return;
     const int strip = item % A.nstrips, band = item / A.nstrips;
     const int r_lo = band * A.band_rows, r_hi = min(A.rows, r_lo + A.band_rows);   // rows of this launch's chunk
     if (r_lo >= r_hi) return;
@@ -363,10 +344,6 @@ corr_march_kernel(ModelDev m, MarchArgs A, Sep1D sep)
         filter_and_store(y);
     }
     wait_vmcnt<0>();
-    if (A.done && tid == 0) {
-        atomicOr(A.done + item, 1ull << pass);
-        if (A.ndone) atomicAdd(A.ndone, 1);
-    }
     if (A.ablate & 4) {
         if (plane_ok && tid == 0) *(UMPA_GLOBAL double*)tbase = ring[0][0] + ring[0][1] + ring[0][2] + ring[0][3];
     }

@@ -4,7 +4,8 @@
 // the pixels of a 32 x 32 tile together a compact blob of them: on BASELINE config C2 about 5-6 of the 9 row offsets,
 // on C3 (15 x 15 shifts) well under half.  A table plane is produced per (tile, pass) -- a pass is one row offset and
 // one batch of column offsets, exactly the unit of work of a corr_volume / corr_masked workgroup -- so whole
-// workgroups can be left out.  Which ones is PREDICTED, and every prediction error is repaired, so the maps are those
+// workgroups can be left out.  (One scheme, for those two table kernels and their replays; corr_march, umpa_march.h,
+// always computes its whole table: DESIGN.md 4.7.)  Which ones is PREDICTED, and every prediction error is repaired, so the maps are those
 // of the exhaustive table bit for bit:
 //
 //   1. seed tiles (every OD_SP-th tile in both directions): all passes are computed (a compact static grid), their
@@ -28,8 +29,7 @@ namespace umpa {
 
 #define OD_SP 4                       // seed-tile spacing
 #define OD_ROUNDS 3                   // repair rounds; the last one computes everything that is still missing
-#define OD_SAMPLE_ROUNDS 3            // corr_march's schedule (od_run_chunk_lattice): rounds of the sample lattice
-#define OD_STAGES 12                  // counter blocks of a chunk (>= OD_ROUNDS + 1 and >= OD_SAMPLE_ROUNDS + OD_ROUNDS + 3)
+#define OD_STAGES (OD_ROUNDS + 1)      // counter blocks of a chunk
 // counters: int[8] per stage, stage 0 = steps 1-3, stage r = repair round r.
 #define OD_C_TILES  0                 // missed tiles listed by the replay of this stage
 #define OD_C_PX     1                 // pixels parked by the replay of this stage
@@ -50,11 +50,14 @@ struct OdArgs {
                                       // replay kernels: 0 no on-demand, 1 seed-tile pixels (compact grid; record visited), 2 the other pixels
                                       // (park on a miss), 3 persistent grid over px_in (park on a miss)
     int tc, ub, nbatch, npass, ntx, nty;   // pass / tile geometry of the table kernel
-    int tr;                           // rows of a tile: 32 (corr_volume, corr_masked) or corr_march's band height (a tile = strip x band)
-    int sub;                          // replay_walk mode 2: > 1 = only the pixels of a lattice, every sub-th in both directions (corr_march's
-                                      // sample stage); 0, 1: every pixel
-    unsigned long long central;       // od_run_chunk_lattice: the passes every tile gets before any walk (those around shift (0, 0))
-    int alone;                        // 1: a parked pixel asks for the pass it missed alone, 0: and for its neighbours in the row-offset direction
+    // The next four had other values only under corr_march's lattice schedule, which is gone.  They and their
+    // tests in od_begin / od_park stay as they were, so that replay_cost keeps its code byte for byte: without them it compiled
+    // to other code that was slower on C2 + mask (four alternated runs each: 1.4443 1.4474 1.4386 1.4399 ms with them,
+    // 1.4546 1.4501 1.4491 1.4588 without).
+    int tr;                           // rows of a tile: always 32 (od_args)
+    int sub;                          // unused
+    unsigned long long central;       // unused
+    int alone;                        // always 0: a parked pixel asks for the pass it missed and for its neighbours in the row-offset direction
     int r0, c0;                       // seed tiles: ty % OD_SP == r0 and tx % OD_SP == c0
     int ub_inv;                       // ceil(2^16 / ub): x / ub = (x * ub_inv) >> 16 for 0 <= x < 70
     int nrow_inv;                     // the same for the row offsets per pass
@@ -97,7 +100,6 @@ __device__ __forceinline__ void od_append(const OdArgs& od, int lin, unsigned lo
     }
 }
 
-// what = 4: the central passes of every tile (od_run_chunk_lattice).
 // what = 1, step 2: the predicted passes of the tiles that are not seed tiles, onto the work list.
 // what = 2, a repair round: the passes the missed tiles' parked pixels asked for; what = 3, the last round: every pass they lack.
 __global__ void __launch_bounds__(256)
@@ -105,10 +107,6 @@ od_list_kernel(OdArgs od, int what)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
     const unsigned long long all = od.npass >= 64 ? ~0ull : (1ull << od.npass) - 1;
-    if (what == 4) {                                                  // od_run_chunk_lattice, stage 0: the central passes of every tile
-        if (q < od.ntx * od.nty) od_append(od, q, od.central & all);
-        return;
-    }
     if (what >= 2) {
         if (q >= gp(od.cnt_in)[OD_C_TILES]) return;
         const int lin = gp(od.tile_in)[q];
@@ -211,7 +209,7 @@ __device__ __forceinline__ void od_park(const OdArgs& od, const OdLane& L, int p
 {
     gpw(od.px_out)[atomicAdd(od.cnt_out + OD_C_PX, 1)] = px;
     unsigned long long want = 1ull << L.miss_pass;
-    if (od.alone == 0) {                                             // (corr_march's passes are several row offsets deep already)
+    if (od.alone == 0) {
         if (L.miss_pass >= od.nbatch) want |= 1ull << (L.miss_pass - od.nbatch);
         if (L.miss_pass + od.nbatch < od.npass) want |= 1ull << (L.miss_pass + od.nbatch);
     }

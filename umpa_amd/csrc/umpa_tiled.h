@@ -342,7 +342,7 @@ __device__ __forceinline__ void lookup_solve(const ModelDev& m, int ref_mode, co
 }
 
 // Workgroup = UMPA_REPLAY_ROWS waves, each on a block of 64 pixels (ReplayArgs::bw_log2: 16 x 4, or 32 x 2 on corr_march's table; the
-// lattice and parked-pixel modes of the on-demand stages: 64 list entries).  A workgroup keeps its LDS until its slowest wave has
+// parked-pixel mode of the on-demand stages: 64 list entries).  A workgroup keeps its LDS until its slowest wave has
 // finished, so small workgroups refill the CU sooner (the walk lengths differ): one wave per workgroup (two: C2 0.93 against 0.91 ms).
 #ifndef UMPA_REPLAY_ROWS
 #define UMPA_REPLAY_ROWS 1
@@ -384,18 +384,13 @@ replay_walk_kernel(ModelDev m, Maps M, ReplayArgs R, RegionArgs A, OdArgs od_in)
         live = live && xi >= R.row0 && xi < R.row0 + R.rows && xj < A.N1;
     } else {
         if (!first) break;
-        if (OD && od.sub > 1) {                                      // the sample lattice (a compact grid, 64 lattice pixels of a row per wave)
-            xj = (blockIdx.x * 64 + threadIdx.x) * od.sub + (od.sub >> 1);
-            xi = (blockIdx.y * UMPA_REPLAY_ROWS + threadIdx.y) * od.sub + (od.sub >> 1);
-        } else {
-            // a wave = a block of 2^bw_log2 x 2^(6 - bw_log2) pixels (ReplayArgs): the window of the maps and of the table that
-            // its walks read is (rows + 2 ms) x (columns + 2 ms) positions -- 288 for 16 x 4 against 648 for 64 x 1 at C2.
-            // (blocks onto XCD-contiguous bands of block rows -- xcd_band_remap -- is slower: C2 0.90 -> 0.98 ms, C3 7.7 -> 9.4; so are
-            //  XCD-contiguous strips of block columns: 0.91 -> 1.08; see the grid's width at the launch)
-            const int bwl = R.bw_log2;
-            xj = (blockIdx.x << bwl) + (threadIdx.x & ((1 << bwl) - 1));
-            xi = ((blockIdx.y * UMPA_REPLAY_ROWS + threadIdx.y) << (6 - bwl)) + (threadIdx.x >> bwl);
-        }
+        // a wave = a block of 2^bw_log2 x 2^(6 - bw_log2) pixels (ReplayArgs): the window of the maps and of the table that
+        // its walks read is (rows + 2 ms) x (columns + 2 ms) positions -- 288 for 16 x 4 against 648 for 64 x 1 at C2.
+        // (blocks onto XCD-contiguous bands of block rows -- xcd_band_remap -- is slower: C2 0.90 -> 0.98 ms, C3 7.7 -> 9.4; so are
+        //  XCD-contiguous strips of block columns: 0.91 -> 1.08; see the grid's width at the launch)
+        const int bwl = R.bw_log2;
+        xj = (blockIdx.x << bwl) + (threadIdx.x & ((1 << bwl) - 1));
+        xi = ((blockIdx.y * UMPA_REPLAY_ROWS + threadIdx.y) << (6 - bwl)) + (threadIdx.x >> bwl);
         xi += R.row0;
         live = xi < R.row0 + R.rows && xj < A.N1;
     }
@@ -481,7 +476,7 @@ replay_walk_kernel(ModelDev m, Maps M, ReplayArgs R, RegionArgs A, OdArgs od_in)
         }
     }
     if (L.miss) od_park(od, L, xi * A.N1 + xj);
-    else if (!(OD && od.sub > 1)) {                                   // (the sample lattice's walks only predict: A.uv is read AND written)
+    else {
         double nb[16];
         walk_finish(w, memo, (R.ablate & 2) ? 0 : m.subpx, nb);
         if (KIND == 1 && (w.live.t != 0.0 || w.live.v != 0.0))      // eval_lookup left K in the v slot; (0,0) = never evaluated
@@ -569,13 +564,11 @@ struct TiledTimers {
 // The tiled path's switches, read once at the start of a match, not cached: the tests switch them between
 // matches.
 struct TiledEnv {
-    int ondemand;             // UMPA_HIP_ONDEMAND: -1 unset, 0, 1, 2 = another value (od_enabled; corr_march's stages: any but 0)
+    int ondemand;             // UMPA_HIP_ONDEMAND: -1 unset, 0, 1, 2 = another value (od_enabled; never under corr_march)
     bool march;               // UMPA_HIP_MARCH: corr_march where it is instantiated (default), 0 never
-    int march_od_rows;        // UMPA_HIP_MARCH_OD_ROWS: band height of corr_march's on-demand units
     size_t table_bytes;       // UMPA_HIP_TABLE_MB: the shift table's budget
     int corr_shape;           // UMPA_HIP_CORR_SHAPE: corr_volume's workgroup shape by number (launch_corr_shape), 0 automatic
     int ablate, ablate_replay, ablate_march, ablate_masked;   // UMPA_HIP_ABLATE(_REPLAY, _MARCH, _MASKED): the kernels' `ablate`
-    bool od_debug;            // UMPA_HIP_OD_DEBUG: corr_march's on-demand counters on stderr (a host wait)
 };
 
 inline TiledEnv tiled_env()
@@ -585,7 +578,6 @@ inline TiledEnv tiled_env()
     const char* od = getenv("UMPA_HIP_ONDEMAND");
     E.ondemand = !od ? -1 : atoi(od) == 0 ? 0 : atoi(od) == 1 ? 1 : 2;
     E.march = num("UMPA_HIP_MARCH", 1) != 0;
-    E.march_od_rows = (int)std::max(32L, num("UMPA_HIP_MARCH_OD_ROWS", 512));
     // 288 GB of HBM: C3's 30 GB table in two chunks (4 GiB: 50.2 -> 49.3 ms)
     E.table_bytes = (size_t)std::max(16L, num("UMPA_HIP_TABLE_MB", 16384)) << 20;
     E.corr_shape = (int)num("UMPA_HIP_CORR_SHAPE", 0);
@@ -593,7 +585,6 @@ inline TiledEnv tiled_env()
     E.ablate_replay = (int)num("UMPA_HIP_ABLATE_REPLAY", 0);
     E.ablate_march = (int)num("UMPA_HIP_ABLATE_MARCH", 0);
     E.ablate_masked = (int)num("UMPA_HIP_ABLATE_MASKED", 0);
-    E.od_debug = getenv("UMPA_HIP_OD_DEBUG") != nullptr;
     return E;
 }
 
@@ -877,9 +868,7 @@ inline hipError_t launch_march_inst(const ModelDev& dev, const MarchArgs& A, con
     constexpr auto kern = &corr_march_kernel<NW, NXB, UMPA_MARCH_NPT, UMPA_MARCH_LA, UMPA_MARCH_NT, 3>;
     const hipError_t e = set_lds_limit_once<kern>(UMPA_LDS_BUDGET, current_device());
     if (e != hipSuccess) return e;
-    const int nitems = A.nstrips * A.nbands;
-    // (work list: a slot for every unit there could be; the workgroups past the list's end leave at once)
-    const int grid = A.items ? 8 * ((nitems * A.npass + 7) / 8) : 8 * ((nitems + 7) / 8) * A.npass;
+    const int grid = 8 * ((A.nstrips * A.nbands + 7) / 8) * A.npass;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(UMPA_MARCH_NT), P.lds, s, dev, A, sep);
     return hipGetLastError();
 }
@@ -910,7 +899,7 @@ inline hipError_t launch_march(const ModelDev& dev, MarchArgs A, const Sep1D& se
         const double cost = rounds * (std::ceil((double)A.rows / nb) + 2 * Nw + 8);
         if (cost < best_cost - 1e-9) { best_cost = cost; best_nb = nb; }
     }
-    if (A.nbands <= 0) { A.nbands = best_nb; A.band_rows = (A.rows + best_nb - 1) / best_nb; }   // (on-demand passes: the bands are the caller's tiles)
+    A.nbands = best_nb; A.band_rows = (A.rows + best_nb - 1) / best_nb;
     if (fma) march_fma(dev, A, fma);
     if (Nw == 6) return P.nxb == 4 ? launch_march_inst<6, 4>(dev, A, sep, P, s) : launch_march_inst<6, 8>(dev, A, sep, P, s);
     return P.nxb == 4 ? launch_march_inst<7, 4>(dev, A, sep, P, s) : launch_march_inst<7, 8>(dev, A, sep, P, s);
@@ -1040,70 +1029,6 @@ inline hipError_t od_run_chunk(OdArgs od, const OdBuffers& B, hipStream_t s, Cor
     return hipSuccess;
 }
 
-// The same without seed tiles, for corr_march, whose unit of work is (strip, band, pass) -- a "tile" is a strip x band, a pass
-// NUY row offsets x every column offset: every walk starts at shift (0, 0), so the prediction can be the walks themselves on a
-// lattice of sample pixels.  (Under corr_volume / corr_masked the seed tiles predict their 32 x 32 tiles better: DESIGN.md.)
-//   0. the passes around shift (0, 0) (od.central), every tile;
-//   1. the pixels of a lattice (every OD_LATTICE_SUB-th in both directions) walk; one that needs a pass that is not there parks and asks
-//      for it (od_park); OD_SAMPLE_ROUNDS rounds of  list -> table kernel over the list -> parked pixels again,  then what
-//      the last round still asked for.  Their cost is 1 / OD_LATTICE_SUB^2 of a replay each; what they leave behind is `done`;
-//      (these walks store nothing: the start shifts A.uv are read AND written by a walk that ends);
-//   2. every pixel walks (the lattice's again: they are 1 / OD_LATTICE_SUB^2 of the pixels); OD_ROUNDS repair rounds as in od_run_chunk,
-//      the last one computing every pass the tiles with parked pixels lack.
-#define OD_LATTICE_SUB 8
-template <class Corr, class Replay>
-inline hipError_t od_run_chunk_lattice(OdArgs od, const OdBuffers& B, hipStream_t s, Corr corr, Replay replay)
-{
-    hipError_t e = hipMemsetAsync(od.done, 0, B.zero_bytes, s);
-    if (e != hipSuccess) return e;
-    const int ntiles = od.ntx * od.nty, lb = (ntiles + 255) / 256;
-    od.r0 = od.c0 = -1;                                               // no seed tiles
-    auto stage = [&](int r) { return B.counters + 8 * r; };
-    int k = 0;                                                        // the stage whose counters were written last
-    auto round = [&](int what, bool walk) {
-        od.cnt_in = stage(k); od.cnt_out = stage(k + 1);
-        od.tile_in = B.tiles[k & 1]; od.tile_out = B.tiles[(k + 1) & 1];
-        od.px_in = B.px[k & 1]; od.px_out = B.px[(k + 1) & 1];
-        hipLaunchKernelGGL(od_list_kernel, dim3(lb), dim3(256), 0, s, od, what);
-        hipError_t re = hipGetLastError();
-        if (re != hipSuccess) return re;
-        od.mode = 2; if ((re = corr(od)) != hipSuccess) return re;
-        if (walk) { od.mode = 3; if ((re = replay(od)) != hipSuccess) return re; }
-        k++;
-        return hipSuccess;
-    };
-    od.cnt_in = nullptr; od.cnt_out = stage(0);
-    od.tile_in = nullptr; od.tile_out = B.tiles[0]; od.px_in = nullptr; od.px_out = B.px[0];
-    hipLaunchKernelGGL(od_list_kernel, dim3(lb), dim3(256), 0, s, od, 4);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    od.mode = 2; if ((e = corr(od)) != hipSuccess) return e;
-    od.sub = OD_LATTICE_SUB; od.mode = 2; if ((e = replay(od)) != hipSuccess) return e;
-    for (int r = 1; r <= OD_SAMPLE_ROUNDS; r++) if ((e = round(2, true)) != hipSuccess) return e;
-    if ((e = round(2, false)) != hipSuccess) return e;                // (also clears the flags and requests of the last round's tiles)
-    od.sub = 0;
-    k++;                                                              // a fresh stage for the walks of every pixel
-    od.cnt_in = nullptr; od.cnt_out = stage(k);
-    od.tile_in = nullptr; od.tile_out = B.tiles[k & 1]; od.px_in = nullptr; od.px_out = B.px[k & 1];
-    od.mode = 2; if ((e = replay(od)) != hipSuccess) return e;
-    for (int r = 1; r <= OD_ROUNDS; r++) if ((e = round(r == OD_ROUNDS ? 3 : 2, true)) != hipSuccess) return e;
-    return hipSuccess;
-}
-
-// the passes that hold the row and column offsets -1 .. +1 and the one further that every walk's 4 x 4 gather reaches
-// (Optim.cpp:41-130: rows / columns min - 1 .. min + 2 of the SHIFT; a pass is counted in offsets = sigma * shift)
-inline unsigned long long od_central_passes(int ms, int sigma, int nrow, int nbatch, int ub, int UJ)
-{
-    unsigned long long mask = 0;
-    const int lo = sigma > 0 ? -1 : -2, hi = sigma > 0 ? 2 : 1;
-    for (int oi = lo; oi <= hi; oi++)
-        for (int oj = lo; oj <= hi; oj++) {
-            const int ri = oi + ms - 1, rj = oj + ms - 1;
-            if (ri < 0 || ri >= UJ || rj < 0 || rj >= UJ) continue;
-            mask |= 1ull << ((ri / nrow) * nbatch + rj / ub);
-        }
-    return mask;
-}
-
 // ---- what a match on the plain and on the masked path share
 
 // The map planes of a match (SamSq, RefSq and, DF, the per-frame WS and MR) and M's geometry.  0 or -3.
@@ -1222,15 +1147,13 @@ inline OdArgs od_args(const CorrLaunch& CL)
 
 // The counters of an on-demand chunk into the next page-locked slot: for umpa_hip_last_stats and, on the last launch of table
 // kernel `name` with `fma_per` FMAs per unit, for the FMA count of a timed match.
-inline hipError_t od_record(TiledState& st, const OdBuffers& B, hipStream_t s, TiledTimers& tt, int name, double fma_per,
-                            const int** slot_out = nullptr)
+inline hipError_t od_record(TiledState& st, const OdBuffers& B, hipStream_t s, TiledTimers& tt, int name, double fma_per)
 {
     int* slot = st.od_host + UMPA_OD_NCNT * (st.od_slot++ % UMPA_OD_SLOTS);
     const hipError_t e = hipMemcpyAsync(slot, B.counters, UMPA_OD_NCNT * sizeof(int), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return e;
     if (st.stat_n < 64) st.stat_slots[st.stat_n++] = slot;
     tt.attach(name, slot, fma_per);
-    if (slot_out) *slot_out = slot;
     return hipSuccess;
 }
 
@@ -1288,9 +1211,6 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
         if (MP.ok && !march_offsets(host_frames, K, sigma, box, MA0)) MP.ok = false;
     }
     if (MP.ok) N1p = MP.nstrips * MP.tw;                               // doubles per dense row and shift
-    // on-demand passes of corr_march (od_run_chunk_lattice): UMPA_HIP_ONDEMAND=1 on, =0 off
-    // (a table consumer reads every plane: no on-demand stages while one is set)
-    const bool march_od = E.ondemand > 0 && MP.ok && MP.npass >= 3 && MP.npass <= 64 && !E.ablate_march && !st.consumer;
     long rows_chunk = 0;
     const int rc = tiled_table(st, E, (size_t)UJ * UJ * N1p, N0d, piece_rows, (size_t)N1p, rows_chunk);
     if (rc != 0) return rc;
@@ -1338,18 +1258,13 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
         auto corr = [&](const OdArgs& od) {
             CL.od = od;
             hipError_t ce = hipErrorInvalidValue;
-            if (MP.ok) {                                              // corr_march (od.mode is 0 here: the on-demand stages are corr_volume's)
+            if (MP.ok) {                                              // corr_march: every unit, always (tiled_chunk is told so below)
                 MarchArgs MA = MA0;
                 MA.row0 = drow0; MA.rows = drows;
-                if (od.done) {                                        // on-demand passes: the caller's bands, a part of the units
-                    MA.nbands = od.nty; MA.band_rows = od.tr;
-                    MA.done = od.done; MA.ndone = od.cnt0 ? od.cnt0 + OD_C_DONE : nullptr;
-                    if (od.mode == 2) { MA.items = od.items; MA.nitems = od.cnt_out + OD_C_ITEMS; }
-                }
                 double fma = 0.0;
                 tt.tic(9);
                 ce = launch_march(dev, MA, st.sep, MP, s, &fma);
-                tt.toc(od.done ? 0.0 : fma);                          // (on-demand: counted from the device's tally, od_record)
+                tt.toc(fma);
                 return ce;
             }
             tt.tic(3);
@@ -1379,8 +1294,6 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
                 else if ((grd.x & 7) == 0) grd.x += 1;
             }
             if (od.mode == 3) grd = dim3(2 * device_cu_count(), 1);   // queue over the parked pixels
-            if (od.mode == 2 && od.sub > 1)                           // corr_march's sample lattice
-                grd = dim3(((A.N1 + od.sub - 1) / od.sub + 63) / 64, ((R.rows + od.sub - 1) / od.sub + UMPA_REPLAY_ROWS - 1) / UMPA_REPLAY_ROWS);
             if (od.mode == 1) { blk = dim3(64, 1); grd = dim3((32 * od.tc + 63) / 64, od_seed_count(od.ntx, od.c0) * od_seed_count(od.nty, od.r0)); if (!grd.y) return hipSuccess; }
             tt.tic(4);
 #define UMPA_REPLAY_NA(n) case n: if (od.mode) hipLaunchKernelGGL((replay_walk_kernel<1, n, true>), grd, blk, 0, s, dev, M, R, A, od); \
@@ -1402,36 +1315,7 @@ inline int tiled_match(TiledState& st, const ModelDev& dev, int kind, int H, int
             return hipGetLastError();
         };
 
-        if (march_od) {                                               // tiles = strips x bands of about UMPA_HIP_MARCH_OD_ROWS rows
-            const int nb = std::max(1, (drows + E.march_od_rows / 2) / E.march_od_rows);
-            OdArgs od = od_args(CL);
-            od.tc = MP.wo; od.tr = (drows + nb - 1) / nb; od.ntx = MP.nstrips; od.nty = nb;
-            od.npass = MP.npass; od.nbatch = 1; od.ub = 64; od.ub_inv = 1024; od.nrow_inv = (65536 + MP.nuy - 1) / MP.nuy;
-            od.alone = 1;
-            od.central = od_central_passes(ms, sigma, MP.nuy, 1, 64, UJ);
-            const int march_tiles = od.ntx * od.nty;
-            if (march_tiles >= 2) {
-                OdBuffers OB;
-                if (od_reserve(st, march_tiles, MP.npass, (size_t)A.N0 * A.N1, od, OB)) return -3;
-                if ((e = od_run_chunk_lattice(od, OB, s, corr, replay)) != hipSuccess) return (int)e;
-                MarchArgs MF;                                         // the FMAs of one unit: an exhaustive launch's over its units
-                memset(&MF, 0, sizeof(MF));                           // (the bands are equal but for the last)
-                MF.rows = drows; MF.nstrips = MP.nstrips; MF.npass = MP.npass; MF.nbands = od.nty; MF.band_rows = od.tr;
-                double f = 0.0;
-                march_fma(dev, MF, &f);
-                const int* slot = nullptr;
-                if ((e = od_record(st, OB, s, tt, 9, f / ((double)march_tiles * MP.npass), &slot)) != hipSuccess) return (int)e;
-                if (E.od_debug) {                                     // diagnostics: the stages' counters (a host wait)
-                    (void)hipStreamSynchronize(s);
-                    fprintf(stderr, "march on-demand: %d tiles (%d strips x %d bands of %d rows) x %d passes\n", march_tiles, od.ntx, od.nty, od.tr, MP.npass);
-                    for (int r = 0; r < OD_STAGES; r++)
-                        fprintf(stderr, "  stage %2d: tiles listed %6d  pixels parked %8d  units listed %6d  units done (stage 0: all) %6d\n",
-                                r, slot[8 * r + OD_C_TILES], slot[8 * r + OD_C_PX], slot[8 * r + OD_C_ITEMS], slot[8 * r + OD_C_DONE]);
-                }
-                st.stat_total_passes += (double)march_tiles * MP.npass;
-                return 0;
-            }
-        }
+        // (no on-demand stages under corr_march, nor while a table consumer is set: it reads every plane)
         return tiled_chunk(st, CL, !MP.ok && !st.consumer && od_enabled(E, ntiles, CL.npass, false) && !CA.ablate, (size_t)A.N0 * A.N1, s, tt, 3, corr, replay);
     });
 }
