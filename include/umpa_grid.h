@@ -7,9 +7,11 @@
  *
  *   umpa_grid_match_region  the global minimum over the (2 max_shift - 1)^2 integer shifts of every pixel, followed by
  *                           the walk's own sub-pixel step on the 4x4 neighbourhood of that minimum;
- *   umpa_grid_cost_volume   the cost (and optionally transmission and dark-field) of every shift at every pixel.
+ *   umpa_grid_cost_volume   the cost (and optionally transmission and dark-field) of every shift at every pixel;
+ *   umpa_grid_basins        per pixel the K lowest local minima ("basins") of the cost over the search box, each with the
+ *                           sub-pixel step and fit umpa_grid_match_region would give it, and the count of all basins.
  *
- * Both work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
+ * All work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
  * one shape at position (0, 0), steps and search ranges within that path's limits.  Anything else fails with
  * UMPA_HIP_E_UNSUPPORTED before a kernel is launched.  Models are created, configured and destroyed through
  * include/umpa_hip.h; link both libraries.  Error text: umpa_hip_last_error() for codes that umpa_hip_match_region
@@ -64,6 +66,39 @@ int umpa_grid_match_region(umpa_hip_model *m, int start0, int step0, int N0, int
  * An array holds U * U * N0 * N1 doubles. */
 int umpa_grid_cost_volume(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
                           double *cost, double *T, double *df, int flags, void *stream);
+
+/* Basin enumeration: per pixel, the K lowest local minima ("basins") of the cost over the search box, 1 <= K <= 8.
+ *
+ * Let C[si][sj], -max_shift < si, sj < max_shift, be the costs of umpa_grid_cost_volume for one pixel.  Scan order is the
+ * grid search's: rows (si) first, then columns (sj).
+ *   Beats.   A neighbour n BEATS a shift s iff C[n] < C[s], or C[n] == C[s] and n precedes s in scan order.
+ *   Basin.   A shift s is a basin iff C[s] < +Inf and none of its up to eight neighbours inside the box beats it.
+ *            Neighbours outside the box do not exist.  Every comparison is a plain `<` or `==` of doubles: a NaN neighbour
+ *            never beats anything and a NaN shift is never a basin; -Inf is a cost like any other.  A run of equal adjacent
+ *            costs yields only its earliest member, and only if nothing else beats that member.
+ *   Ranking. Basins are ordered by cost ascending, by scan order among equal costs.  The first K are kept; count is the
+ *            number of ALL basins of the pixel and may exceed K.
+ *   Consequence: rank 0 is the integer minimum of umpa_grid_match_region.  The first strict minimum has nothing below it
+ *            and no equal cost before it, so nothing beats it; no basin costs less, and an equally cheap one comes later.
+ *   Per kept basin, the epilogue of umpa_grid_match_region around it instead of around the global minimum: the quadrant
+ *            rule picks the 4x4 neighbourhood, dx, dy, f come from the sub-pixel fit the model is set to (mode 0: the
+ *            integer shift, f = 1 - ip), T (and df) are those of the integer shift, err = 1; err = 0 where that 4x4
+ *            neighbourhood leaves the search range: dx, dy are the integer shift, f its cost.  A NaN among the cells
+ *            around a basin is treated as umpa_grid_match_region treats it.  cost is always the cost of the integer shift.
+ *   Slots k >= count: err = -1, every double 0, the shift (0, 0).  A pixel without any finite cost: count = 0, all slots
+ *            empty.
+ *
+ * The model and the region as for umpa_grid_cost_volume.  Outputs are planes [K][N0][N1]: doubles f, T, dx (column shift),
+ * dy (row shift), cost and df (may be NULL; dark-field model only: UMPA_HIP_E_* with a plain model); ints si (row), sj
+ * (column), err; and count[N0][N1].  Host arrays, or device arrays with UMPA_HIP_F_DEVICE_IO (the call then only enqueues
+ * work on `stream`); UMPA_HIP_F_USE_STAGED as for umpa_grid_cost_volume; any other flag is UMPA_HIP_E_ARG.  Checked in this
+ * order, before anything touches a device: a NULL model or array (other than df), K outside 1 .. 8, the flags -- each
+ * UMPA_HIP_E_ARG.  No coverage map: the models this library admits are covered everywhere.
+ * One pass over the table, no atomics: the output is the same bit for bit from run to run, for host and device arrays and
+ * under any row chunking. */
+int umpa_grid_basins(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1, int K,
+                     double *f, double *T, double *dx, double *dy, double *cost, double *df,
+                     int *si, int *sj, int *err, int *count, int flags, void *stream);
 
 const char *umpa_grid_last_error(void);
 

@@ -17,6 +17,8 @@ pixel, on ``libumpa_ddf.so``: the directional dark-field signal.
 volume on ``libumpa_smooth.so`` and start the ordinary walk from it.
 ``uncertainty`` (``umpa_amd.sigma``) gives the per-pixel standard deviations of ``dx``, ``dy`` and a noise estimate, on
 ``libumpa_sigma.so``; ``Uncertainty.weight()`` feeds ``phase_from_match``.
+``model.basins()`` gives, per pixel, the K lowest local minima of the cost over the search box, on ``libumpa_grid.so``;
+``umpa_amd.basins`` holds the helpers that pick among them (``nearest``, ``select``, ``start_shifts``, ``ambiguity``).
 """
 from . import model
 from . import align
@@ -31,9 +33,11 @@ from . import smooth
 from .smooth import aggregate, cost_scale, match_smooth
 from . import sigma
 from .sigma import uncertainty, Uncertainty
+from . import basins
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
            "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration",
            "ddf", "KernelSearch", "gaussian_kernel", "kernel_from_sigma", "sigma_from_kernel", "candidate_grid", "blur_frames",
            "smooth", "aggregate", "cost_scale", "match_smooth",
-           "sigma", "uncertainty", "Uncertainty"]
+           "sigma", "uncertainty", "Uncertainty",
+           "basins"]

@@ -1,8 +1,8 @@
 // umpa_grid.hip -- libumpa_grid.so: exhaustive grid search and the cost volume (include/umpa_grid.h).  gfx950 only.
 //
-// A second library, built from the headers of libumpa_hip.so by the same build: it holds the two kernel families of
-// umpa_grid_kernels.h and no other feature code.  A call sets itself as the model's table consumer (umpa_hipx.h), runs
-// umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
+// A second library, built from the headers of libumpa_hip.so by the same build: it holds the kernel families of
+// umpa_grid_kernels.h and umpa_basins_kernels.h and no other feature code.  A call sets itself as the model's table
+// consumer (umpa_hipx.h), runs umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -11,6 +11,7 @@
 #include "umpa_host.h"
 #include "umpa_hipx.h"
 #include "umpa_grid_kernels.h"
+#include "umpa_basins_kernels.h"
 
 using namespace umpa;
 
@@ -27,13 +28,33 @@ struct GridJob {
     double* dev[3] = {nullptr, nullptr, nullptr};
     size_t count = 0;                 // doubles per array
     const char* refused = nullptr;
+    // umpa_grid_basins: grid_basins_kernel instead of either; host arrays: one device block for all ten outputs
+    bool basins = false;
+    BasinArgs B = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    bool want_df = false;
+    void* block = nullptr;
 };
+
+// the ten output arrays of umpa_grid_basins in the order of its arguments: six of doubles, then four of ints ([K] planes, count one)
+void basins_carve(BasinArgs& B, void* block, size_t plane, int K, bool df)
+{
+    double* d = (double*)block;
+    B.f = d; B.T = d + K * plane; B.dx = d + 2 * K * plane; B.dy = d + 3 * K * plane; B.cost = d + 4 * K * plane;
+    B.df = df ? d + 5 * K * plane : nullptr;
+    int* q = (int*)(d + 6 * K * plane);
+    B.si = q; B.sj = q + K * plane; B.err = q + 2 * K * plane; B.count = q + 3 * K * plane;
+}
+size_t basins_bytes(size_t plane, int K) { return 6 * K * plane * sizeof(double) + (3 * K + 1) * plane * sizeof(int); }
 
 // the frame count as a template constant exactly where replay_walk's dispatch has it (tiled_match)
 template <int KIND, int NA>
 void launch(const GridJob& J, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
 {
-    if (J.volume) {
+    if (J.basins) {
+        const int bw = 1 << R.bw_log2, bh = 64 >> R.bw_log2;
+        hipLaunchKernelGGL((grid_basins_kernel<KIND, NA>), dim3((A.N1 + bw - 1) / bw, (R.rows + bh - 1) / bh), dim3(64),
+                           grid_basins_lds(dev.ms), s, dev, M, R, A, J.B);
+    } else if (J.volume) {
         hipLaunchKernelGGL((cost_volume_kernel<KIND, NA>), dim3((A.N1 + 63) / 64, R.rows), dim3(64), 0, s, dev, M, R, A, J.V);
     } else {
         const int bw = 1 << R.bw_log2, bh = 64 >> R.bw_log2;
@@ -54,6 +75,15 @@ hipError_t consumer(void* user, const ModelDev& dev, const Maps& M, const Replay
             for (int q = 0; q < 3; q++)
                 if (J.want[q] && hipMalloc((void**)&J.dev[q], J.count * sizeof(double)) != hipSuccess) { J.dev[q] = nullptr; return hipErrorOutOfMemory; }
             J.V.cost = J.dev[0]; J.V.T = J.dev[1]; J.V.df = J.dev[2];
+        }
+    }
+    if (J.basins) {
+        if (J.want_df && kind != 1) { J.refused = "basins: a dark-field map (df) needs the dark-field model"; return hipErrorInvalidValue; }
+        if (grid_basins_lds(dev.ms) > 64 * 1024) { J.refused = "basins: the search box does not fit the kernel's ring of cost rows"; return hipErrorInvalidValue; }
+        J.B.plane = (size_t)A.N0 * A.N1;
+        if (J.host && !J.block) {
+            if (hipMalloc(&J.block, basins_bytes(J.B.plane, J.B.K)) != hipSuccess) { J.block = nullptr; return hipErrorOutOfMemory; }
+            basins_carve(J.B, J.block, J.B.plane, J.B.K, J.want_df);
         }
     }
     if (R.rows <= 0 || A.N1 <= 0) return hipSuccess;
@@ -136,5 +166,52 @@ UMPA_GRID_API int umpa_grid_cost_volume(umpa_hip_model* m, int start0, int step0
         for (int q = 0; q < 3; q++) if (J.dev[q]) (void)hipFree(J.dev[q]);
     }
     if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the cost volume: %s", hipGetErrorString(e));
+    return rc;
+}
+
+UMPA_GRID_API int umpa_grid_basins(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int K,
+                                   double* f, double* T, double* dx, double* dy, double* cost, double* df,
+                                   int* si, int* sj, int* err, int* count, int flags, void* stream)
+{
+    if (!m || !f || !T || !dx || !dy || !cost || !si || !sj || !err || !count) return fail(UMPA_HIP_E_ARG, "grid: basins: null argument");
+    if (K < 1 || K > UMPA_GRID_MAX_BASINS)
+        return fail(UMPA_HIP_E_ARG, "grid: basins keeps 1 to %d basins per pixel, not %d", UMPA_GRID_MAX_BASINS, K);
+    if (flags & ~(UMPA_HIP_F_DEVICE_IO | UMPA_HIP_F_USE_STAGED))
+        return fail(UMPA_HIP_E_ARG, "grid: basins takes UMPA_HIP_F_DEVICE_IO, UMPA_HIP_F_USE_STAGED and no other flag");
+    const int staged = flags & UMPA_HIP_F_USE_STAGED;
+    GridJob J;
+    J.basins = true;
+    J.B.K = K;
+    J.want_df = df != nullptr;
+    // value and status placeholders for the match entry point, as in umpa_grid_cost_volume: with device I/O nothing reads,
+    // seeds or clears them
+    double* const no_values = cost;
+    int* const no_err = (int*)cost;
+    if (flags & UMPA_HIP_F_DEVICE_IO) {
+        J.B.f = f; J.B.T = T; J.B.dx = dx; J.B.dy = dy; J.B.cost = cost; J.B.df = df;
+        J.B.si = si; J.B.sj = sj; J.B.err = err; J.B.count = count;
+        return run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                   UMPA_HIP_F_DEVICE_IO | staged, stream);
+    }
+    // host arrays: one device block for the duration of the call, allocated by the consumer on the model's device (which
+    // stays this thread's current device), filled on that device's null stream
+    J.host = true;
+    int rc = run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                 UMPA_HIP_F_DEVICE_IO | staged, nullptr);
+    if (!J.block) return rc;                                          // refused before the consumer ran: nothing was enqueued
+    hipError_t e = hipSuccess;
+    if (rc >= 0) {
+        const size_t kp = (size_t)K * J.B.plane;
+        const struct { void* host; const void* dev; size_t bytes; } copies[10] = {
+            {f, J.B.f, kp * sizeof(double)}, {T, J.B.T, kp * sizeof(double)}, {dx, J.B.dx, kp * sizeof(double)},
+            {dy, J.B.dy, kp * sizeof(double)}, {cost, J.B.cost, kp * sizeof(double)}, {df, J.B.df, kp * sizeof(double)},
+            {si, J.B.si, kp * sizeof(int)}, {sj, J.B.sj, kp * sizeof(int)}, {err, J.B.err, kp * sizeof(int)},
+            {count, J.B.count, J.B.plane * sizeof(int)}};
+        for (int q = 0; q < 10 && e == hipSuccess; q++)
+            if (copies[q].host && copies[q].dev) e = hipMemcpy(copies[q].host, copies[q].dev, copies[q].bytes, hipMemcpyDeviceToHost);
+    }
+    if (rc < 0 || e != hipSuccess) (void)hipDeviceSynchronize();      // nothing of this call may still use the block freed here
+    (void)hipFree(J.block);
+    if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the basins: %s", hipGetErrorString(e));
     return rc;
 }

@@ -480,9 +480,43 @@ class UMPAModelBase:
         keys = ['cost'] + (['T'] + (['df'] if self._kind == KIND_DF else []) if with_fit else [])
         return self._grid_cost_volume(ROI, step, lambda U, N0, N1: {k: np.empty((U, U, N0, N1), dtype=NPDOUBLE) for k in keys})[2]
 
+    def _grid_basins(self, k, ROI, step, alloc):
+        """The one ``umpa_grid_basins`` call.  ``alloc(k, N0, N1)`` gives the output arrays once the model, ``k`` and the region
+        have passed: a dictionary of ``f``, ``T``, ``dx``, ``dy``, ``cost`` (and ``df``: dark-field model) as float64
+        ``[k, N0, N1]``, ``si``, ``sj``, ``err`` as int32 ``[k, N0, N1]`` and ``count`` as int32 ``[N0, N1]`` -- host arrays, or
+        HIP tensors that the library fills on the current stream.  This call is given the staged stack, so it spends the
+        one-shot flag.  Returns ``(s0, s1, arrays)``."""
+        self._grid_check("basins")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not _lib.GRID_MIN_K <= k <= _lib.GRID_MAX_K:
+            raise ValueError("basins: k must be an integer from %d to %d, not %r" % (_lib.GRID_MIN_K, _lib.GRID_MAX_K, k))
+        k = int(k)
+        s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
+        out = alloc(k, N0, N1)
+        _, flags, stream = _lib.Side(out['cost'], device=self._device).tail(self._staged_flag())
+        names = ('f', 'T', 'dx', 'dy', 'cost', 'df', 'si', 'sj', 'err', 'count')
+        try:
+            _lib.grid().check(_lib.grid().basins(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1, k,
+                                                 *[_lib.Side.ptr(out.get(n)) for n in names], flags, stream), "grid basins")
+        except _lib.NativeError as e:
+            raise RuntimeError("basins: %s" % e) from None
+        return s0, s1, out
+
+    def _basins(self, k=4, ROI=None, step=None):
+        dbl = ['f', 'T', 'dx', 'dy', 'cost'] + (['df'] if self._kind == KIND_DF else [])
+
+        def alloc(k, N0, N1):                                      # page-locked, as the result maps of match(): downloaded at PCIe rate
+            out = {n: _lib.pinned_empty((k, N0, N1), NPDOUBLE) for n in dbl}
+            out.update({n: _lib.pinned_empty((k, N0, N1), np.int32) for n in ('si', 'sj', 'err')})
+            out['count'] = _lib.pinned_empty((N0, N1), np.int32)
+            return out
+
+        out = self._grid_basins(k, ROI, step, alloc)[2]
+        out['shift'] = np.stack([out.pop('si'), out.pop('sj')], axis=1)
+        return out
+
     _force = 0
     _use_staged = False
-    _sam_staged = False         # the sample stack came from stage_sample: self._sam is not the stack the library matches
+    _sam_staged = False        # the sample stack came from stage_sample: self._sam is not the stack the library matches
     _async = False
     _out_alloc = None           # hook (shape, dtype, zero) -> array for the result maps (farm.py: shared-memory result slots)
 
@@ -522,7 +556,7 @@ class UMPAModelBase:
         float32 / uint16 (page-locked arrays -- ``_lib.pinned_empty`` -- make this return at once); ``dark`` / ``flat``:
         device float64 stacks (lists of 2-D HIP tensors) for the fused ``(raw - dark) / flat`` of ``umpa_multi.py:144``.
         The staged stack becomes the sample stack of the next call that reads the sample stack -- ``match()``,
-        ``cost_volume()``, ``match_smooth`` -- and stays it.  The last stack wins: another ``stage_sample`` or
+        ``cost_volume()``, ``basins()``, ``match_smooth`` -- and stays it.  The last stack wins: another ``stage_sample`` or
         ``update_frames(sam_list=...)`` before that call replaces it.  The model keeps no host copy of a staged stack:
         ``uncertainty()`` then needs it as ``sam=``."""
         if not self._lib.is_hip or hasattr(self._sam[0], "data_ptr"):
@@ -706,6 +740,27 @@ class _UMPAModelPlain(UMPAModelBase):
         Models the plain tiled path takes whole only (no masks, no ``pos_list``, steps and search ranges within its
         limits); anything else raises ``RuntimeError``."""
         return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
+
+    def basins(self, k=4, ROI=None, step=None):
+        """Per pixel, the ``k`` lowest local minima ("basins") of the cost over the search box (extension;
+        ``include/umpa_grid.h`` has the definition): a shift is a basin iff its cost is below ``+Inf`` and none of its up
+        to eight neighbours inside the box has a lower cost, or an equal one earlier in scan order (rows first, then
+        columns).  Basins are ranked by cost, then scan order; rank 0 is the integer minimum of ``match(search='grid')``.
+        Returns a dictionary of
+
+          ``dx``, ``dy``, ``f``, ``T`` (``df``: dark-field model)  float64 ``[k, N0, N1]``: what ``match(search='grid')``
+                    would return had rank ``r`` been the minimum -- the model's sub-pixel step on the 4x4 neighbourhood of
+                    the basin (``dy``: row shift, ``dx``: column shift), ``T`` / ``df`` of the integer shift;
+          ``cost``  float64 ``[k, N0, N1]``: the cost of the integer shift, ``cost_volume()``'s number;
+          ``shift`` int32 ``[k, 2, N0, N1]``: the integer shift, row shift first;
+          ``err``   int32 ``[k, N0, N1]``: 1 the fit succeeded, 0 the 4x4 neighbourhood leaves the search range (``dx``,
+                    ``dy`` are the integer shift, ``f`` its cost), -1 the pixel has no basin of this rank (zeros);
+          ``count`` int32 ``[N0, N1]``: the number of basins of the pixel, which may exceed ``k``.
+
+        ``k``: 1 to 8.  ``ROI`` / ``step`` as for ``cost_volume()``; the model's own ROI is not changed; a stack uploaded by
+        ``stage_sample`` is adopted as by ``cost_volume()``.  Models ``cost_volume()`` takes only; anything else raises
+        ``RuntimeError``.  ``umpa_amd.basins`` has helpers that pick among the ranks."""
+        return self._basins(k=k, ROI=ROI, step=step)
 
     def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
         """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
