@@ -9,7 +9,9 @@
  *                           the walk's own sub-pixel step on the 4x4 neighbourhood of that minimum;
  *   umpa_grid_cost_volume   the cost (and optionally transmission and dark-field) of every shift at every pixel;
  *   umpa_grid_basins        per pixel the K lowest local minima ("basins") of the cost over the search box, each with the
- *                           sub-pixel step and fit umpa_grid_match_region would give it, and the count of all basins.
+ *                           sub-pixel step and fit umpa_grid_match_region would give it, and the count of all basins;
+ *   umpa_grid_track         per pixel, among ALL its basins, the one nearest a prior shift (or the best under cost plus a
+ *                           distance penalty), finished like a kept basin: one set of maps, the prior may live on the device.
  *
  * All work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
  * one shape at position (0, 0), steps and search ranges within that path's limits.  Anything else fails with
@@ -99,6 +101,51 @@ int umpa_grid_cost_volume(umpa_hip_model *m, int start0, int step0, int N0, int 
 int umpa_grid_basins(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1, int K,
                      double *f, double *T, double *dx, double *dy, double *cost, double *df,
                      int *si, int *sj, int *err, int *count, int flags, void *stream);
+
+/* Tracked search: per pixel, among ALL basins of the cost over the search box, the one a prior shift selects.
+ *
+ * C[si][sj], "beats", "basin" and scan order are those of umpa_grid_basins, unchanged.
+ *   Prior.   (p_i, p_j) per pixel: two planes [N0][N1] of doubles indexed like the outputs, p_i the row shift, p_j the
+ *            column shift, in the units of the shifts (si, sj) of umpa_grid_basins.  Those are also the units of the maps
+ *            dy (rows) and dx (columns) of umpa_hip_match_region, under either coordinate assignment: with the reference
+ *            coordinates ('ref') the kernels move the other stack's window, but a pixel's result is stored as the shift the
+ *            search indexed, without a change of sign or of origin.  So (dy, dx) of an earlier match, or of an earlier
+ *            call of this function, on the same model settings is a prior as it stands: p_i = dy, p_j = dx.
+ *   Distance. d2(s) = (si - p_i) * (si - p_i) + (sj - p_j) * (sj - p_j) in doubles: two subtractions, two products, one
+ *            addition, each rounded (no fused multiply-add).  A pixel whose p_i or p_j is NaN has d2(s) = 0 for every
+ *            shift: it falls back to the data term alone.  An infinite prior is a number like any other (d2 = +Inf).
+ *   Admissible. radius < 0: every basin.  Otherwise a basin s is admissible iff d2(s) <= r2, r2 = radius * radius formed
+ *            once.
+ *   Choice.  The admissible basins are gone through in scan order; the first is the best so far, and a later one replaces
+ *            the best iff it is strictly better:
+ *              UMPA_GRID_TRACK_NEAREST (0): d2(s) < d2(best), or d2(s) == d2(best) and C[s] < C[best] -- the smallest d2,
+ *                then the smallest cost, then scan order: the rule of umpa_amd.basins.nearest, over all basins;
+ *              UMPA_GRID_TRACK_PENALTY (1): key(s) < key(best), key(s) = C[s] + lam * d2(s), one product and one addition,
+ *                each rounded -- the smallest key, then scan order.  With lam = 0 (and finite priors) this is rank 0 of
+ *                umpa_grid_basins, the integer minimum of umpa_grid_match_region.  A NaN key (0 * Inf, Inf - Inf) is never
+ *                `<` anything and nothing is `<` it.
+ *            Every comparison is a plain `<`, `<=` or `==` of doubles.
+ *   Outputs, planes [N0][N1].  For the chosen basin f, T, dx, dy, cost, df (doubles) and si, sj, err (ints), exactly what
+ *            umpa_grid_basins writes for a kept basin: quadrant rule, 4x4 neighbourhood, the model's sub-pixel mode, T (df)
+ *            of the integer shift, err = 1, or err = 0 with the integer shift and its cost where the 4x4 leaves the box.
+ *            cost0: the lowest cost of any basin of the pixel (rank 0's); cost > cost0 says the prior overruled the data
+ *            term.  count: all basins of the pixel.  found: its admissible basins.
+ *            found == 0: err = -1, f = T = dx = dy = cost (= df) = 0, si = sj = 0; cost0 and count are written all the
+ *            same; count == 0: cost0 = 0.
+ *
+ * The model and the region as for umpa_grid_basins.  Host arrays, or device arrays with UMPA_HIP_F_DEVICE_IO (the call then
+ * only enqueues work on `stream`) -- the priors and the outputs alike; UMPA_HIP_F_USE_STAGED as for umpa_grid_cost_volume.
+ * df may be NULL (dark-field model only: UMPA_HIP_E_* with a plain model).  Checked in this order, before anything touches
+ * a device, each UMPA_HIP_E_ARG: a NULL model or array (other than df); a mode other than 0 and 1; with mode 1, a lam that
+ * is not finite or is negative (mode 0 ignores lam); a NaN radius; a flag other than the two above.
+ * One pass over the table, no atomics: the output is the same bit for bit from run to run, for host and device arrays and
+ * under any row chunking. */
+#define UMPA_GRID_TRACK_NEAREST 0
+#define UMPA_GRID_TRACK_PENALTY 1
+int umpa_grid_track(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
+                    const double *prior_i, const double *prior_j, int mode, double lam, double radius,
+                    double *f, double *T, double *dx, double *dy, double *cost, double *df,
+                    int *si, int *sj, int *err, double *cost0, int *count, int *found, int flags, void *stream);
 
 const char *umpa_grid_last_error(void);
 

@@ -19,6 +19,8 @@ volume on ``libumpa_smooth.so`` and start the ordinary walk from it.
 ``libumpa_sigma.so``; ``Uncertainty.weight()`` feeds ``phase_from_match``.
 ``model.basins()`` gives, per pixel, the K lowest local minima of the cost over the search box, on ``libumpa_grid.so``;
 ``umpa_amd.basins`` holds the helpers that pick among them (``nearest``, ``select``, ``start_shifts``, ``ambiguity``).
+``model.track()`` makes that choice on the device, among all basins, from a per-pixel prior; ``Tracker`` / ``prior_from``
+(``umpa_amd.track``) run a step series on it, each projection's shifts being the next one's prior.
 """
 from . import model
 from . import align
@@ -34,10 +36,13 @@ from .smooth import aggregate, cost_scale, match_smooth
 from . import sigma
 from .sigma import uncertainty, Uncertainty
 from . import basins
+from . import track
+from .track import Tracker, prior_from
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
            "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration",
            "ddf", "KernelSearch", "gaussian_kernel", "kernel_from_sigma", "sigma_from_kernel", "candidate_grid", "blur_frames",
            "smooth", "aggregate", "cost_scale", "match_smooth",
            "sigma", "uncertainty", "Uncertainty",
-           "basins"]
+           "basins",
+           "track", "Tracker", "prior_from"]

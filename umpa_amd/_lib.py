@@ -158,10 +158,12 @@ def _satellite(name, table):
 # include/umpa_grid.h: the exhaustive grid search and the cost volume, on models of libumpa_hip.so
 GRID_LIB_PATH = os.path.join(_HERE, "libumpa_grid.so")
 GRID_MIN_K, GRID_MAX_K = 1, 8                                    # UMPA_GRID_MAX_BASINS
+GRID_TRACK_NEAREST, GRID_TRACK_PENALTY = 0, 1                    # UMPA_GRID_TRACK_*
 _GRID_ABI = {
     "match_region": (_int, _model_abi(True)["match_region"][1]),
     "cost_volume": (_int, [_vp] + [_int] * 6 + [_vp] * 3 + [_int, _vp]),
     "basins": (_int, [_vp] + [_int] * 7 + [_vp] * 10 + [_int, _vp]),
+    "track": (_int, [_vp] + [_int] * 6 + [_vp] * 2 + [_int, _dbl, _dbl] + [_vp] * 12 + [_int, _vp]),
     "last_error": (C.c_char_p, []),
 }
 GRID_SYMBOLS = list(_GRID_ABI)

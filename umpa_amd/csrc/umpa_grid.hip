@@ -1,7 +1,7 @@
 // umpa_grid.hip -- libumpa_grid.so: exhaustive grid search and the cost volume (include/umpa_grid.h).  gfx950 only.
 //
 // A second library, built from the headers of libumpa_hip.so by the same build: it holds the kernel families of
-// umpa_grid_kernels.h and umpa_basins_kernels.h and no other feature code.  A call sets itself as the model's table
+// umpa_grid_kernels.h, umpa_basins_kernels.h and umpa_track_kernels.h and no other feature code.  A call sets itself as the model's table
 // consumer (umpa_hipx.h), runs umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 #include "umpa_hipx.h"
 #include "umpa_grid_kernels.h"
 #include "umpa_basins_kernels.h"
+#include "umpa_track_kernels.h"
 
 using namespace umpa;
 
@@ -33,6 +34,13 @@ struct GridJob {
     BasinArgs B = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     bool want_df = false;
     void* block = nullptr;
+    // umpa_grid_track: grid_track_kernel; host arrays: one device block for the two priors and the twelve outputs, the
+    // priors uploaded by the consumer before the first chunk's kernel
+    bool track = false;
+    TrackArgs K = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                   0, 0, 0.0, 0.0};
+    const double* host_pi = nullptr;
+    const double* host_pj = nullptr;
 };
 
 // the ten output arrays of umpa_grid_basins in the order of its arguments: six of doubles, then four of ints ([K] planes, count one)
@@ -46,11 +54,29 @@ void basins_carve(BasinArgs& B, void* block, size_t plane, int K, bool df)
 }
 size_t basins_bytes(size_t plane, int K) { return 6 * K * plane * sizeof(double) + (3 * K + 1) * plane * sizeof(int); }
 
+// umpa_grid_track's block: nine planes of doubles (the priors, then the seven double outputs in the order of its
+// arguments), then five of ints
+void track_carve(TrackArgs& K, void* block, size_t plane, bool df)
+{
+    double* d = (double*)block;
+    K.pi = d; K.pj = d + plane;
+    K.f = d + 2 * plane; K.T = d + 3 * plane; K.dx = d + 4 * plane; K.dy = d + 5 * plane; K.cost = d + 6 * plane;
+    K.df = df ? d + 7 * plane : nullptr;
+    K.cost0 = d + 8 * plane;
+    int* q = (int*)(d + 9 * plane);
+    K.si = q; K.sj = q + plane; K.err = q + 2 * plane; K.count = q + 3 * plane; K.found = q + 4 * plane;
+}
+size_t track_bytes(size_t plane) { return 9 * plane * sizeof(double) + 5 * plane * sizeof(int); }
+
 // the frame count as a template constant exactly where replay_walk's dispatch has it (tiled_match)
 template <int KIND, int NA>
 void launch(const GridJob& J, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
 {
-    if (J.basins) {
+    if (J.track) {
+        const int bw = 1 << R.bw_log2, bh = 64 >> R.bw_log2;
+        hipLaunchKernelGGL((grid_track_kernel<KIND, NA>), dim3((A.N1 + bw - 1) / bw, (R.rows + bh - 1) / bh), dim3(64),
+                           grid_basins_lds(dev.ms), s, dev, M, R, A, J.K);
+    } else if (J.basins) {
         const int bw = 1 << R.bw_log2, bh = 64 >> R.bw_log2;
         hipLaunchKernelGGL((grid_basins_kernel<KIND, NA>), dim3((A.N1 + bw - 1) / bw, (R.rows + bh - 1) / bh), dim3(64),
                            grid_basins_lds(dev.ms), s, dev, M, R, A, J.B);
@@ -84,6 +110,18 @@ hipError_t consumer(void* user, const ModelDev& dev, const Maps& M, const Replay
         if (J.host && !J.block) {
             if (hipMalloc(&J.block, basins_bytes(J.B.plane, J.B.K)) != hipSuccess) { J.block = nullptr; return hipErrorOutOfMemory; }
             basins_carve(J.B, J.block, J.B.plane, J.B.K, J.want_df);
+        }
+    }
+    if (J.track) {
+        if (J.want_df && kind != 1) { J.refused = "track: a dark-field map (df) needs the dark-field model"; return hipErrorInvalidValue; }
+        if (grid_basins_lds(dev.ms) > 64 * 1024) { J.refused = "track: the search box does not fit the kernel's ring of cost rows"; return hipErrorInvalidValue; }
+        if (J.host && !J.block) {
+            const size_t plane = (size_t)A.N0 * A.N1;
+            if (hipMalloc(&J.block, track_bytes(plane)) != hipSuccess) { J.block = nullptr; return hipErrorOutOfMemory; }
+            track_carve(J.K, J.block, plane, J.want_df);
+            hipError_t e = hipMemcpy((void*)J.K.pi, J.host_pi, plane * sizeof(double), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy((void*)J.K.pj, J.host_pj, plane * sizeof(double), hipMemcpyHostToDevice);
+            if (e != hipSuccess) return e;
         }
     }
     if (R.rows <= 0 || A.N1 <= 0) return hipSuccess;
@@ -213,5 +251,63 @@ UMPA_GRID_API int umpa_grid_basins(umpa_hip_model* m, int start0, int step0, int
     if (rc < 0 || e != hipSuccess) (void)hipDeviceSynchronize();      // nothing of this call may still use the block freed here
     (void)hipFree(J.block);
     if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the basins: %s", hipGetErrorString(e));
+    return rc;
+}
+
+UMPA_GRID_API int umpa_grid_track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                  const double* prior_i, const double* prior_j, int mode, double lam, double radius,
+                                  double* f, double* T, double* dx, double* dy, double* cost, double* df,
+                                  int* si, int* sj, int* err, double* cost0, int* count, int* found, int flags, void* stream)
+{
+    if (!m || !prior_i || !prior_j || !f || !T || !dx || !dy || !cost || !si || !sj || !err || !cost0 || !count || !found)
+        return fail(UMPA_HIP_E_ARG, "grid: track: null argument");
+    if (mode != UMPA_GRID_TRACK_NEAREST && mode != UMPA_GRID_TRACK_PENALTY)
+        return fail(UMPA_HIP_E_ARG, "grid: track: mode must be UMPA_GRID_TRACK_NEAREST (0) or UMPA_GRID_TRACK_PENALTY (1), not %d", mode);
+    if (mode == UMPA_GRID_TRACK_PENALTY && !(lam >= 0.0 && lam < __builtin_inf()))
+        return fail(UMPA_HIP_E_ARG, "grid: track: lam must be finite and not negative");
+    if (radius != radius) return fail(UMPA_HIP_E_ARG, "grid: track: radius must not be NaN");
+    if (flags & ~(UMPA_HIP_F_DEVICE_IO | UMPA_HIP_F_USE_STAGED))
+        return fail(UMPA_HIP_E_ARG, "grid: track takes UMPA_HIP_F_DEVICE_IO, UMPA_HIP_F_USE_STAGED and no other flag");
+    const int staged = flags & UMPA_HIP_F_USE_STAGED;
+    GridJob J;
+    J.track = true;
+    J.want_df = df != nullptr;
+    J.K.mode = mode;
+    J.K.lam = mode == UMPA_GRID_TRACK_PENALTY ? lam : 0.0;
+    J.K.limited = radius < 0.0 ? 0 : 1;
+    J.K.r2 = radius < 0.0 ? 0.0 : radius * radius;
+    // value and status placeholders for the match entry point, as in umpa_grid_cost_volume: with device I/O nothing reads,
+    // seeds or clears them
+    double* const no_values = cost;
+    int* const no_err = (int*)cost;
+    if (flags & UMPA_HIP_F_DEVICE_IO) {
+        J.K.pi = prior_i; J.K.pj = prior_j;
+        J.K.f = f; J.K.T = T; J.K.dx = dx; J.K.dy = dy; J.K.cost = cost; J.K.df = df; J.K.cost0 = cost0;
+        J.K.si = si; J.K.sj = sj; J.K.err = err; J.K.count = count; J.K.found = found;
+        return run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                   UMPA_HIP_F_DEVICE_IO | staged, stream);
+    }
+    // host arrays: one device block for the duration of the call, allocated and given the priors by the consumer on the
+    // model's device (which stays this thread's current device), filled on that device's null stream
+    J.host = true;
+    J.host_pi = prior_i; J.host_pj = prior_j;
+    int rc = run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                 UMPA_HIP_F_DEVICE_IO | staged, nullptr);
+    if (!J.block) return rc;                                          // refused before the consumer ran: nothing was enqueued
+    hipError_t e = hipSuccess;
+    if (rc >= 0) {
+        const size_t plane = (size_t)N0 * N1;
+        const struct { void* host; const void* dev; size_t bytes; } copies[12] = {
+            {f, J.K.f, plane * sizeof(double)}, {T, J.K.T, plane * sizeof(double)}, {dx, J.K.dx, plane * sizeof(double)},
+            {dy, J.K.dy, plane * sizeof(double)}, {cost, J.K.cost, plane * sizeof(double)}, {df, J.K.df, plane * sizeof(double)},
+            {cost0, J.K.cost0, plane * sizeof(double)},
+            {si, J.K.si, plane * sizeof(int)}, {sj, J.K.sj, plane * sizeof(int)}, {err, J.K.err, plane * sizeof(int)},
+            {count, J.K.count, plane * sizeof(int)}, {found, J.K.found, plane * sizeof(int)}};
+        for (int q = 0; q < 12 && e == hipSuccess; q++)
+            if (copies[q].host && copies[q].dev) e = hipMemcpy(copies[q].host, copies[q].dev, copies[q].bytes, hipMemcpyDeviceToHost);
+    }
+    if (rc < 0 || e != hipSuccess) (void)hipDeviceSynchronize();      // nothing of this call may still use the block freed here
+    (void)hipFree(J.block);
+    if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the track maps: %s", hipGetErrorString(e));
     return rc;
 }

@@ -514,6 +514,87 @@ class UMPAModelBase:
         out['shift'] = np.stack([out.pop('si'), out.pop('sj')], axis=1)
         return out
 
+    def _grid_track(self, prior, mode, lam, radius, ROI, step, alloc):
+        """The one ``umpa_grid_track`` call.  ``prior(N0, N1)`` gives the two prior planes (row shift, column shift) and
+        ``alloc(N0, N1)`` the output arrays once the model and the region have passed: float64 ``[N0, N1]`` each, the
+        outputs a dictionary of ``f``, ``T``, ``dx``, ``dy``, ``cost``, ``cost0`` (and ``df``: dark-field model) as float64 and
+        ``si``, ``sj``, ``err``, ``count``, ``found`` as int32 -- all host arrays, or all HIP tensors that the library reads and
+        fills on the current stream.  This call is given the staged stack, so it spends the one-shot flag.
+        Returns ``(s0, s1, arrays)``."""
+        self._grid_check("track")
+        s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
+        pi, pj = prior(N0, N1)
+        out = alloc(N0, N1)
+        _, flags, stream = _lib.Side(pi, pj, *out.values(), device=self._device,
+                                     mixed="track: the priors and the outputs must be all host arrays or all HIP tensors").tail(self._staged_flag())
+        names = ('f', 'T', 'dx', 'dy', 'cost', 'df', 'si', 'sj', 'err', 'cost0', 'count', 'found')
+        try:
+            _lib.grid().check(_lib.grid().track(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1,
+                                                _lib.Side.ptr(pi), _lib.Side.ptr(pj), int(mode), float(lam), float(radius),
+                                                *[_lib.Side.ptr(out.get(n)) for n in names], flags, stream), "grid track")
+        except _lib.NativeError as e:
+            raise RuntimeError("track: %s" % e) from None
+        return s0, s1, out
+
+    def _track(self, prior_dx, prior_dy, lam=None, radius=None, ROI=None, step=None):
+        self._grid_check("track")
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+        if lam is not None and not (number(lam) and 0.0 <= float(lam) < np.inf):
+            raise ValueError("track: lam must be None (the nearest basin) or a finite number >= 0, not %r" % (lam,))
+        if radius is not None and not (number(radius) and float(radius) >= 0.0):
+            raise ValueError("track: radius must be None (no limit) or a number >= 0, not %r" % (radius,))
+        mode = _lib.GRID_TRACK_NEAREST if lam is None else _lib.GRID_TRACK_PENALTY
+        given = (prior_dy, prior_dx)                                # the library's order: row shift first
+        on_device = [hasattr(p, "data_ptr") for p in given]
+        if any(on_device) and not all(d or np.ndim(p) == 0 for p, d in zip(given, on_device)):
+            raise ValueError("track: the priors must be both numpy arrays (or scalars) or both HIP tensors")
+        dev = next((p.device for p, d in zip(given, on_device) if d), None)
+
+        def prior(N0, N1):
+            planes = []
+            for p, d in zip(given, on_device):
+                shape = tuple(p.shape) if d else np.shape(p)
+                if shape not in ((), (N0, N1)):
+                    raise ValueError("track: a prior must be a scalar or of shape %s, not %s" % ((N0, N1), shape))
+                if d:
+                    import torch
+                    if p.dtype != torch.float64 or not p.is_cuda or p.device.index != self._device:
+                        raise ValueError("track: a device prior must be a float64 HIP tensor on the model's device")
+                    planes.append(p.expand(N0, N1).contiguous())
+                elif dev is not None:
+                    import torch
+                    planes.append(torch.full((N0, N1), float(p), dtype=torch.float64, device=dev))
+                else:
+                    a = np.asarray(p)
+                    if a.dtype.kind not in "fiu":
+                        raise ValueError("track: a prior must be of a real number type, not %s" % a.dtype)
+                    planes.append(np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=NPDOUBLE), (N0, N1))))   # (no copy of a float64 plane)
+            return planes
+
+        dbl = ['f', 'T', 'dx', 'dy', 'cost', 'cost0'] + (['df'] if self._kind == KIND_DF else [])
+        ints = ('si', 'sj', 'err', 'count', 'found')
+
+        def alloc(N0, N1):
+            if dev is not None:
+                import torch
+                out = {n: torch.empty((N0, N1), dtype=torch.float64, device=dev) for n in dbl}
+                out.update({n: torch.empty((N0, N1), dtype=torch.int32, device=dev) for n in ints})
+                return out
+            out = {n: _lib.pinned_empty((N0, N1), NPDOUBLE) for n in dbl}   # page-locked, as the result maps of match()
+            out.update({n: _lib.pinned_empty((N0, N1), np.int32) for n in ints})
+            return out
+
+        out = self._grid_track(prior, mode, 0.0 if lam is None else lam, -1.0 if radius is None else radius, ROI, step, alloc)[2]
+        si, sj, err = out.pop('si'), out.pop('sj'), out.pop('err')
+        if dev is not None:
+            import torch
+            out['shift'] = torch.stack([si, sj], dim=0)
+            out['err'] = torch.clamp(err, min=0)
+        else:
+            out['shift'] = np.stack([si, sj], axis=0)
+            out['err'] = np.maximum(err, 0)
+        return out
+
     _force = 0
     _use_staged = False
     _sam_staged = False        # the sample stack came from stage_sample: self._sam is not the stack the library matches
@@ -556,7 +637,7 @@ class UMPAModelBase:
         float32 / uint16 (page-locked arrays -- ``_lib.pinned_empty`` -- make this return at once); ``dark`` / ``flat``:
         device float64 stacks (lists of 2-D HIP tensors) for the fused ``(raw - dark) / flat`` of ``umpa_multi.py:144``.
         The staged stack becomes the sample stack of the next call that reads the sample stack -- ``match()``,
-        ``cost_volume()``, ``basins()``, ``match_smooth`` -- and stays it.  The last stack wins: another ``stage_sample`` or
+        ``cost_volume()``, ``basins()``, ``track()``, ``match_smooth`` -- and stays it.  The last stack wins: another ``stage_sample`` or
         ``update_frames(sam_list=...)`` before that call replaces it.  The model keeps no host copy of a staged stack:
         ``uncertainty()`` then needs it as ``sam=``."""
         if not self._lib.is_hip or hasattr(self._sam[0], "data_ptr"):
@@ -761,6 +842,31 @@ class _UMPAModelPlain(UMPAModelBase):
         ``stage_sample`` is adopted as by ``cost_volume()``.  Models ``cost_volume()`` takes only; anything else raises
         ``RuntimeError``.  ``umpa_amd.basins`` has helpers that pick among the ranks."""
         return self._basins(k=k, ROI=ROI, step=step)
+
+    def track(self, prior_dx, prior_dy, lam=None, radius=None, ROI=None, step=None):
+        """Tracked search (extension; ``include/umpa_grid.h``: ``umpa_grid_track`` has the definition): per pixel, among ALL
+        basins of the cost over the search box -- not only the eight ``basins()`` can keep -- the one a prior shift
+        ``(prior_dy rows, prior_dx columns)`` selects, finished like ``match(search='grid')`` finishes its minimum.  One pass on
+        the device, one set of maps back.
+
+          ``lam=None``    the basin nearest the prior (then the cheaper one, then scan order): ``basins.nearest`` over all basins;
+          ``lam=number``  the basin with the smallest ``cost + lam * d2``, ``d2`` the squared distance of its integer shift from
+                          the prior; ``lam=0`` is ``match(search='grid')``;
+          ``radius``      only basins with ``d2 <= radius ** 2`` are admissible (``None``: all).
+
+        The priors are in the units of ``dx`` / ``dy`` of ``match()`` under either ``assign_coordinates``, so an earlier
+        result's maps are priors as they stand (``umpa_amd.track.prior_from`` marks its failed pixels).  Scalars or
+        ``[N0, N1]`` arrays of the region; numpy arrays, or float64 HIP tensors on the model's device -- then the maps come back
+        as HIP tensors too.  A NaN prior leaves the pixel to the data term (the grid search's answer).
+
+        Returns the dictionary of ``match()`` -- ``dx``, ``dy``, ``f``, ``T`` (``df``), ``err`` -- plus ``cost`` (of the chosen
+        integer shift), ``cost0`` (the lowest basin cost of the pixel: ``cost > cost0`` says the prior overruled the data
+        term), ``shift`` int32 ``[2, N0, N1]`` (row shift first), ``count`` (all basins) and ``found`` (the admissible ones).
+        ``err`` is 1 where the sub-pixel fit succeeded and 0 otherwise, as ``match()`` has it; ``found == 0`` tells a pixel
+        without an admissible basin (zeros) from one whose 4x4 neighbourhood leaves the search range.
+
+        ``ROI`` / ``step``, the staged stack and the admitted models as for ``basins()``."""
+        return self._track(prior_dx, prior_dy, lam=lam, radius=radius, ROI=ROI, step=step)
 
     def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
         """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
