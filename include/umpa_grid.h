@@ -12,6 +12,8 @@
  *                           sub-pixel step and fit umpa_grid_match_region would give it, and the count of all basins;
  *   umpa_grid_track         per pixel, among ALL its basins, the one nearest a prior shift (or the best under cost plus a
  *                           distance penalty), finished like a kept basin: one set of maps, the prior may live on the device.
+ *   umpa_grid_wide_<name>   each of the four on a shift table and maps box-averaged over the (2b + 1)^2 dense pixels around a
+ *                           pixel: the same search under a window b pixels wider, on the same model ("window widening").
  *
  * All work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
  * one shape at position (0, 0), steps and search ranges within that path's limits.  Anything else fails with
@@ -146,6 +148,54 @@ int umpa_grid_track(umpa_hip_model *m, int start0, int step0, int N0, int start1
                     const double *prior_i, const double *prior_j, int mode, double lam, double radius,
                     double *f, double *T, double *dx, double *dy, double *cost, double *df,
                     int *si, int *sj, int *err, double *cost0, int *count, int *found, int flags, void *stream);
+
+/* Window widening: the four consumers above on a box-pooled shift table.
+ *
+ * b is 0 to UMPA_GRID_MAX_WIDEN, B = 2b + 1, rB = 1.0 / (double)(B * B).  For a plane q on the region's dense (unit-step)
+ * grid, in doubles:
+ *   H(r, c)  = q(r, c-b) + q(r, c-b+1) + ... + q(r, c+b), added left to right;
+ *   V(r, c)  = H(r-b, c) + H(r-b+1, c) + ... + H(r+b, c), added top to bottom;
+ *   q'(r, c) = V(r, c) * rB.
+ * Every operation is rounded, nothing is contracted into a fused multiply-add, and there are no running sums (add the new
+ * element, subtract the old one depends on where the sum started): q' is this sum in this order for every element,
+ * whatever row chunks the table was computed in.
+ * The planes are every plane of the shift table at a fixed shift, t5(., s), and the maps the tiled path keeps per pixel:
+ * SamSq, RefSq and each frame's WS and MR.  A cost, its transmission and dark-field are then the
+ * one evaluation every consumer above already uses (eval_lookup, umpa_amd/csrc/umpa_tiled.h), on the pooled planes.
+ * All these planes are windowed sums, linear in the window w, so q' is the same quantity under the window
+ *   W' = (w (*) box_B) / B^2   ((*): convolution),
+ * which is separable, has the sum of w and the half-width Nw + b.  The results are therefore those of the reference model
+ * with window W' (up to rounding; tests/widen_expect.py has the bound), at the same pixel and shift.
+ *
+ * Border.  A pixel of the region whose B x B block of dense pixels leaves the region's dense grid (the first and last b
+ * dense rows and columns) has NaN table entries, hence NaN costs, and the siblings' rules for NaN apply:
+ *   umpa_grid_wide_match_region  err = 0 and zeros;       umpa_grid_wide_cost_volume  NaN (cost, T and df);
+ *   umpa_grid_wide_basins        count = 0, empty slots;  umpa_grid_wide_track        found = 0, err = -1 (count = 0, cost0 = 0).
+ * A caller who wants numbers there asks for a region b dense pixels larger on every side (umpa_amd.widen does).
+ *
+ * Each function is its sibling with `int b` after N1, and with b = 0 it is the sibling, bit for bit.  Checked in this order
+ * before anything touches a device: the sibling's NULL arguments (same text), b outside 0 .. UMPA_GRID_MAX_WIDEN
+ * (UMPA_HIP_E_ARG, the text names the value), then the sibling's other checks in their order.
+ * The pooled planes live in workspace from the device's stream-ordered allocator (hipMallocAsync on the call's stream at
+ * the first row chunk, given back on that stream behind the last kernel): with UMPA_HIP_F_DEVICE_IO the call still only
+ * enqueues work.  The output is the same bit for bit from run to run, for host and device arrays and under any row chunking.
+ * With b > 0 a dense row is finished one row chunk late.  umpa_grid_wide_match_region on host arrays therefore downloads
+ * its maps when all chunks are enqueued, not chunk by chunk, and returns with the maps complete also under
+ * UMPA_HIP_F_ASYNC; a rows callback (umpa_hip_set_rows_callback) may be told of rows that the next chunk completes. */
+#define UMPA_GRID_MAX_WIDEN 8
+int umpa_grid_wide_match_region(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+                                double *values, int nparam, double *uv, int *err,
+                                const double *covermap, double cover_threshold,
+                                double *dbg_d, double *dbg_a, int *dbg_ncalls, int flags, void *stream);
+int umpa_grid_wide_cost_volume(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+                               double *cost, double *T, double *df, int flags, void *stream);
+int umpa_grid_wide_basins(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1, int b, int K,
+                          double *f, double *T, double *dx, double *dy, double *cost, double *df,
+                          int *si, int *sj, int *err, int *count, int flags, void *stream);
+int umpa_grid_wide_track(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+                         const double *prior_i, const double *prior_j, int mode, double lam, double radius,
+                         double *f, double *T, double *dx, double *dy, double *cost, double *df,
+                         int *si, int *sj, int *err, double *cost0, int *count, int *found, int flags, void *stream);
 
 const char *umpa_grid_last_error(void);
 

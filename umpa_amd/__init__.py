@@ -21,6 +21,8 @@ volume on ``libumpa_smooth.so`` and start the ordinary walk from it.
 ``umpa_amd.basins`` holds the helpers that pick among them (``nearest``, ``select``, ``start_shifts``, ``ambiguity``).
 ``model.track()`` makes that choice on the device, among all basins, from a per-pixel prior; ``Tracker`` / ``prior_from``
 (``umpa_amd.track``) run a step series on it, each projection's shifts being the next one's prior.
+``widen=b`` on ``match(search='grid')``, ``cost_volume``, ``basins`` and ``track`` searches under a window ``b`` pixels wider,
+on the same model; ``umpa_amd.widen`` has that window, the region of a widened result and ``coarse_to_fine``.
 """
 from . import model
 from . import align
@@ -38,6 +40,7 @@ from .sigma import uncertainty, Uncertainty
 from . import basins
 from . import track
 from .track import Tracker, prior_from
+from . import widen
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
            "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration",
@@ -45,4 +48,5 @@ __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAMo
            "smooth", "aggregate", "cost_scale", "match_smooth",
            "sigma", "uncertainty", "Uncertainty",
            "basins",
-           "track", "Tracker", "prior_from"]
+           "track", "Tracker", "prior_from",
+           "widen"]

@@ -166,6 +166,10 @@ _GRID_ABI = {
     "track": (_int, [_vp] + [_int] * 6 + [_vp] * 2 + [_int, _dbl, _dbl] + [_vp] * 12 + [_int, _vp]),
     "last_error": (C.c_char_p, []),
 }
+# umpa_grid_wide_<name>: the sibling's arguments with `int b` after N1 (the seventh argument)
+GRID_MAX_WIDEN = 8                                               # UMPA_GRID_MAX_WIDEN
+for _name in ("match_region", "cost_volume", "basins", "track"):
+    _GRID_ABI["wide_" + _name] = (_int, _GRID_ABI[_name][1][:7] + [_int] + _GRID_ABI[_name][1][7:])
 GRID_SYMBOLS = list(_GRID_ABI)
 
 # include/umpa_unwarp.h: detector distortion correction, stand-alone and fused into stage_sample of models of libumpa_hip.so

@@ -1,7 +1,7 @@
 // umpa_grid.hip -- libumpa_grid.so: exhaustive grid search and the cost volume (include/umpa_grid.h).  gfx950 only.
 //
 // A second library, built from the headers of libumpa_hip.so by the same build: it holds the kernel families of
-// umpa_grid_kernels.h, umpa_basins_kernels.h and umpa_track_kernels.h and no other feature code.  A call sets itself as the model's table
+// umpa_grid_kernels.h, umpa_basins_kernels.h, umpa_track_kernels.h and umpa_widen_kernels.h and no other feature code.  A call sets itself as the model's table
 // consumer (umpa_hipx.h), runs umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@
 #include "umpa_grid_kernels.h"
 #include "umpa_basins_kernels.h"
 #include "umpa_track_kernels.h"
+#include "umpa_widen_kernels.h"
 
 using namespace umpa;
 
@@ -41,7 +42,39 @@ struct GridJob {
                    0, 0, 0.0, 0.0};
     const double* host_pi = nullptr;
     const double* host_pj = nullptr;
+    // window widening (umpa_grid_wide_*, b > 0): the consumer's kernels run on the box-pooled table and maps.  One workspace
+    // from the stream-ordered allocator, taken at the first chunk on the call's stream and given back on it when the call
+    // has enqueued its last kernel: the pooled table of a call's rows, the carry (the chunk's last 2b raw rows), the pooled maps
+    int b = 0;
+    void* ws = nullptr;
+    hipStream_t ws_stream = nullptr;
+    double* pool = nullptr;
+    double* carry = nullptr;
+    double* wmaps = nullptr;
+    int pool_rows = 0, next_drow0 = 0;
+    // umpa_grid_wide_match_region on host arrays: a pooled row is finished one chunk late, so the match entry point's
+    // chunk-by-chunk download would fetch rows before they are written.  The maps go to one device block instead (allocated
+    // by the consumer on the model's device) and are downloaded when all is enqueued.
+    bool mhost = false;
+    RegionArgs mh = {};               // the caller's host arrays (values, err, cover, dbg_*) and nparam
+    void* mblock = nullptr;
+    RegionArgs md = {};               // their device twins
 };
+
+// the block of umpa_grid_wide_match_region's host path: values, dbg_d, dbg_a, cover (doubles), then err, dbg_n (ints)
+size_t match_carve(RegionArgs& d, const RegionArgs& h, void* block, size_t n)
+{
+    double* q = (double*)block;
+    d = h;
+    d.values = q; q += n * h.nparam;
+    d.dbg_d = h.dbg_d ? q : nullptr; q += h.dbg_d ? n * 25 : 0;
+    d.dbg_a = h.dbg_a ? q : nullptr; q += h.dbg_a ? n * 16 : 0;
+    d.cover = h.cover ? q : nullptr; q += h.cover ? n : 0;
+    int* r = (int*)q;
+    d.err = r; r += n;
+    d.dbg_n = h.dbg_n ? r : nullptr; r += h.dbg_n ? n : 0;
+    return (size_t)((char*)r - (char*)block);
+}
 
 // the ten output arrays of umpa_grid_basins in the order of its arguments: six of doubles, then four of ints ([K] planes, count one)
 void basins_carve(BasinArgs& B, void* block, size_t plane, int K, bool df)
@@ -88,10 +121,98 @@ void launch(const GridJob& J, const ModelDev& dev, const Maps& M, const ReplayAr
     }
 }
 
-hipError_t consumer(void* user, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
+// Window widening, one row chunk: the pooled maps (first chunk; prep_maps has filled the raw ones for the whole region), the
+// pooled table of the dense rows whose block is complete (widen_rows), the carry for the next chunk.  `Mw`, `Rw`: what the
+// consumer's kernel gets in place of M and R -- the plain table layout, the output rows among the pooled ones.
+hipError_t widen_chunk(GridJob& J, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s,
+                       Maps& Mw, ReplayArgs& Rw)
+{
+    const int b = J.b, U = 2 * dev.ms - 1, KP = (dev.Na + 1) / 2;
+    const bool df = M.WS != nullptr;
+    WidenGeom g;
+    g.b = b; g.U2 = U * U;
+    g.N0d = A.step0 * (A.N0 - 1) + 1; g.N1d = A.step1 * (A.N1 - 1) + 1;
+    g.drow0 = R.drow0; g.drows = R.drows; g.crows = R.drow0 == 0 ? 0 : 2 * b;
+    g.strip_w = R.strip_w; g.tw = R.tw; g.N1p = R.N1d; g.N1q = (g.N1d + 31) / 32 * 32;
+    widen_rows(b, g.N0d, g.drow0, g.drows, g.p0, g.p1);
+    const bool last = R.drow0 + R.drows >= g.N0d;
+    if (R.drow0 != J.next_drow0 || (!last && R.drows < 2 * b)) { J.refused = "widen: the row chunks do not follow each other"; return hipErrorInvalidValue; }
+    const size_t plane = (size_t)M.H * M.W, nmap = (2 + (df ? 4 * (size_t)KP : 0)) * plane;
+#define UMPA_WIDEN_HB(...) switch (b) { case 1: { constexpr int HB = 1; __VA_ARGS__; } break; case 2: { constexpr int HB = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int HB = 3; __VA_ARGS__; } break; case 4: { constexpr int HB = 4; __VA_ARGS__; } break; case 5: { constexpr int HB = 5; __VA_ARGS__; } break; \
+        case 6: { constexpr int HB = 6; __VA_ARGS__; } break; case 7: { constexpr int HB = 7; __VA_ARGS__; } break; case 8: { constexpr int HB = 8; __VA_ARGS__; } break; }
+    if (!J.ws) {
+        J.pool_rows = std::min(g.N0d, g.drows + b);
+        if ((size_t)J.pool_rows * g.N1q >= ((size_t)1 << 32)) { J.refused = "widen: a plane of the pooled table passes the 32-bit stride of the lookups"; return hipErrorInvalidValue; }
+        const size_t pool_len = (size_t)g.U2 * J.pool_rows * g.N1q, carry_len = last ? 0 : widen_table_len(g, 2 * b);
+        hipError_t e = hipMallocAsync(&J.ws, (pool_len + carry_len + nmap) * sizeof(double), s);
+        if (e != hipSuccess) { J.ws = nullptr; return hipErrorOutOfMemory; }
+        J.ws_stream = s;
+        J.pool = (double*)J.ws; J.carry = J.pool + pool_len; J.wmaps = J.carry + carry_len;
+        // the pooled maps: zero where nothing is pooled (only pixels whose table entries are NaN read there)
+        if ((e = hipMemsetAsync(J.wmaps, 0, nmap * sizeof(double), s)) != hipSuccess) return e;
+        WidenMapArgs a;
+        a.W = M.W; a.plane = plane;
+        a.r0 = std::max(A.org0 - (dev.ms - 1) + b, b); a.r1 = std::min(A.org0 + g.N0d - 1 + (dev.ms - 1) - b + 1, M.H - b);
+        a.c0 = std::max(A.org1 - (dev.ms - 1) + b, b); a.c1 = std::min(A.org1 + g.N1d - 1 + (dev.ms - 1) - b + 1, M.W - b);
+        if (a.r0 < a.r1 && a.c0 < a.c1) {
+            const dim3 grd((a.c1 - a.c0 + 63) / 64, (a.r1 - a.r0 + UMPA_WIDEN_SEG - 1) / UMPA_WIDEN_SEG, 2);
+            UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_map_kernel<HB, false>), grd, dim3(64), 0, s, (const void*)M.SamSq, (void*)J.wmaps, a))
+            if (df) {                                                 // (tiled_maps) WS and MR lie behind each other: 2 KP planes of pairs
+                const dim3 grp(grd.x, grd.y, 2 * KP);
+                UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_map_kernel<HB, true>), grp, dim3(64), 0, s, (const void*)M.WS, (void*)(J.wmaps + 2 * plane), a))
+            }
+        }
+    }
+    if (g.p1 - g.p0 > J.pool_rows) { J.refused = "widen: a row chunk larger than the first"; return hipErrorInvalidValue; }
+    if (g.p1 > g.p0) {
+        const dim3 grd((g.N1q + 63) / 64, g.U2, (g.p1 - g.p0 + UMPA_WIDEN_SEG - 1) / UMPA_WIDEN_SEG);
+        if (R.strip_w > 0) { UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_table_kernel<HB, true>), grd, dim3(64), 0, s, R.table, (const double*)J.carry, J.pool, g)) }
+        else { UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_table_kernel<HB, false>), grd, dim3(64), 0, s, R.table, (const double*)J.carry, J.pool, g)) }
+    }
+#undef UMPA_WIDEN_HB
+    if (!last) {
+        const WidenCarryCopy cc = widen_carry_copy(g);
+        hipLaunchKernelGGL(widen_carry_kernel, dim3((unsigned)((cc.run + 255) / 256), (unsigned)cc.nruns), dim3(256), 0, s, R.table, J.carry, cc);
+    }
+    J.next_drow0 = R.drow0 + R.drows;
+    Mw.SamSq = J.wmaps; Mw.RefSq = J.wmaps + plane;
+    Mw.WS = df ? J.wmaps + 2 * plane : nullptr;
+    Mw.MR = df ? J.wmaps + (2 + 2 * (size_t)KP) * plane : nullptr;
+    Rw.table = J.pool; Rw.slot_stride = (size_t)(g.p1 - g.p0) * g.N1q; Rw.drow0 = g.p0; Rw.N1d = g.N1q;
+    Rw.strip_w = 0; Rw.tw = 0; Rw.drows = g.p1 - g.p0;
+    Rw.bw_log2 = 4;                                                   // the plain table's block shape (tiled_match)
+    Rw.row0 = (g.p0 + A.step0 - 1) / A.step0;
+    Rw.rows = g.p1 > g.p0 ? std::max(0, std::min(A.N0, (g.p1 - 1) / A.step0 + 1) - Rw.row0) : 0;
+    return hipGetLastError();
+}
+
+hipError_t consumer(void* user, const ModelDev& dev, const Maps& M0, const ReplayArgs& R0, const RegionArgs& A0, hipStream_t s)
 {
     GridJob& J = *(GridJob*)user;
+    Maps M = M0;
+    ReplayArgs R = R0;
+    RegionArgs A = A0;
     const int kind = M.WS ? 1 : 0;
+    if (J.mhost) {
+        const size_t n = (size_t)A.N0 * A.N1;
+        if (!J.mblock) {
+            J.mh.nparam = A.nparam;
+            if (hipMalloc(&J.mblock, match_carve(J.md, J.mh, nullptr, n)) != hipSuccess) { J.mblock = nullptr; return hipErrorOutOfMemory; }
+            (void)match_carve(J.md, J.mh, J.mblock, n);
+            if (J.mh.cover) {                                         // pixels under the threshold keep what the caller's arrays hold
+                hipError_t e = hipMemcpy(J.md.values, J.mh.values, n * A.nparam * sizeof(double), hipMemcpyHostToDevice);
+                if (e == hipSuccess) e = hipMemcpy(J.md.err, J.mh.err, n * sizeof(int), hipMemcpyHostToDevice);
+                if (e == hipSuccess) e = hipMemcpy((void*)J.md.cover, J.mh.cover, n * sizeof(double), hipMemcpyHostToDevice);
+                if (e == hipSuccess && J.md.dbg_d) e = hipMemset(J.md.dbg_d, 0, n * 25 * sizeof(double));
+                if (e == hipSuccess && J.md.dbg_a) e = hipMemset(J.md.dbg_a, 0, n * 16 * sizeof(double));
+                if (e == hipSuccess && J.md.dbg_n) e = hipMemset(J.md.dbg_n, 0, n * sizeof(int));
+                if (e != hipSuccess) return e;
+            }
+        }
+        A.values = J.md.values; A.err = J.md.err; A.cover = J.md.cover;
+        A.dbg_d = J.md.dbg_d; A.dbg_a = J.md.dbg_a; A.dbg_n = J.md.dbg_n;
+    }
     if (J.volume) {
         if (J.want[2] && kind != 1) { J.refused = "a dark-field volume needs the dark-field model"; return hipErrorInvalidValue; }
         const int U = 2 * dev.ms - 1;
@@ -124,6 +245,10 @@ hipError_t consumer(void* user, const ModelDev& dev, const Maps& M, const Replay
             if (e != hipSuccess) return e;
         }
     }
+    if (J.b > 0) {
+        const hipError_t e = widen_chunk(J, dev, M0, R0, A, s, M, R);
+        if (e != hipSuccess) return e;
+    }
     if (R.rows <= 0 || A.N1 <= 0) return hipSuccess;
     const bool small = (size_t)M.H * M.W * 2 * sizeof(double) < ((size_t)1 << 32);   // a pair plane (tiled_match)
 #define UMPA_GRID_NA(n) case n: launch<1, n>(J, dev, M, R, A, s); break;
@@ -149,28 +274,48 @@ int run(umpa_hip_model* m, GridJob& J, int start0, int step0, int N0, int start1
     const int rc = umpa_hip_match_region(m, start0, step0, N0, start1, step1, N1, values, nparam, nullptr, err, covermap, thr,
                                          dbg_d, dbg_a, dbg_n, flags | UMPA_HIP_F_FORCE_TILED, stream);
     (void)umpa_hipx_set_table_consumer(m, nullptr, nullptr);
+    if (J.ws) { (void)hipFreeAsync(J.ws, J.ws_stream); J.ws = nullptr; }   // (widening) behind the call's last kernel on its stream
     if (rc < 0) return fail(rc, "grid: %s", J.refused ? J.refused : umpa_hip_last_error());
     return rc;
 }
 
-} // namespace
-
-UMPA_GRID_API const char* umpa_grid_last_error(void) { return g_err.c_str(); }
-
-UMPA_GRID_API int umpa_grid_match_region(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
-                                         double* values, int nparam, double* uv, int* err,
-                                         const double* covermap, double cover_threshold,
-                                         double* dbg_d, double* dbg_a, int* dbg_ncalls, int flags, void* stream)
+// The entry points, each with the half-width `b` of the widening box: 0 for umpa_grid_<name>, whose checks and texts these
+// are; umpa_grid_wide_<name> has checked `b` before.
+int match_region(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+                 double* values, int nparam, double* uv, int* err, const double* covermap, double cover_threshold,
+                 double* dbg_d, double* dbg_a, int* dbg_ncalls, int flags, void* stream)
 {
     if (!m) return fail(UMPA_HIP_E_ARG, "grid: null model");
     if (uv) return fail(UMPA_HIP_E_ARG, "grid search takes no start shifts (uv must be NULL)");
     GridJob J;
-    return run(m, J, start0, step0, N0, start1, step1, N1, values, nparam, err, covermap, cover_threshold,
-               dbg_d, dbg_a, dbg_ncalls, flags, stream);
+    J.b = b;
+    if (b == 0 || (flags & UMPA_HIP_F_DEVICE_IO))
+        return run(m, J, start0, step0, N0, start1, step1, N1, values, nparam, err, covermap, cover_threshold,
+                   dbg_d, dbg_a, dbg_ncalls, flags, stream);
+    // widened, host arrays (GridJob::mhost): the match entry point sees device I/O on the null stream, the consumer swaps
+    // in its block; the maps are complete when the call returns, so UMPA_HIP_F_ASYNC has nothing left to wait for
+    J.mhost = true;
+    J.mh.values = values; J.mh.err = err; J.mh.cover = covermap; J.mh.dbg_d = dbg_d; J.mh.dbg_a = dbg_a; J.mh.dbg_n = dbg_ncalls;
+    int rc = run(m, J, start0, step0, N0, start1, step1, N1, values, nparam, err, covermap, cover_threshold,
+                 dbg_d, dbg_a, dbg_ncalls, (flags & ~UMPA_HIP_F_ASYNC) | UMPA_HIP_F_DEVICE_IO, nullptr);
+    if (!J.mblock) return rc;                                         // refused before the consumer ran: nothing was enqueued
+    hipError_t e = hipSuccess;
+    if (rc >= 0) {
+        const size_t n = (size_t)N0 * N1;
+        const struct { void* host; const void* dev; size_t bytes; } copies[5] = {
+            {values, J.md.values, n * nparam * sizeof(double)}, {err, J.md.err, n * sizeof(int)}, {dbg_d, J.md.dbg_d, n * 25 * sizeof(double)},
+            {dbg_a, J.md.dbg_a, n * 16 * sizeof(double)}, {dbg_ncalls, J.md.dbg_n, n * sizeof(int)}};
+        for (int q = 0; q < 5 && e == hipSuccess; q++)
+            if (copies[q].host && copies[q].dev) e = hipMemcpy(copies[q].host, copies[q].dev, copies[q].bytes, hipMemcpyDeviceToHost);
+    }
+    if (rc < 0 || e != hipSuccess) (void)hipDeviceSynchronize();      // nothing of this call may still use the block freed here
+    (void)hipFree(J.mblock);
+    if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the result maps: %s", hipGetErrorString(e));
+    return rc;
 }
 
-UMPA_GRID_API int umpa_grid_cost_volume(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
-                                        double* cost, double* T, double* df, int flags, void* stream)
+int cost_volume(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+                double* cost, double* T, double* df, int flags, void* stream)
 {
     if (!m || !cost) return fail(UMPA_HIP_E_ARG, "grid: null argument");
     if (flags & ~(UMPA_HIP_F_DEVICE_IO | UMPA_HIP_F_USE_STAGED))
@@ -178,6 +323,7 @@ UMPA_GRID_API int umpa_grid_cost_volume(umpa_hip_model* m, int start0, int step0
     // a staged sample stack is adopted by the match entry point underneath, as by any match: the volume is then that stack's
     const int staged = flags & UMPA_HIP_F_USE_STAGED;
     GridJob J;
+    J.b = b;
     J.volume = true;
     // the match entry point wants value and status arrays; this consumer's kernel touches neither, and with device I/O the
     // entry point hands the pointers to the kernels as they are, nothing is copied, seeded or cleared (noted at that branch
@@ -207,9 +353,9 @@ UMPA_GRID_API int umpa_grid_cost_volume(umpa_hip_model* m, int start0, int step0
     return rc;
 }
 
-UMPA_GRID_API int umpa_grid_basins(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int K,
-                                   double* f, double* T, double* dx, double* dy, double* cost, double* df,
-                                   int* si, int* sj, int* err, int* count, int flags, void* stream)
+int basins(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int b, int K,
+           double* f, double* T, double* dx, double* dy, double* cost, double* df,
+           int* si, int* sj, int* err, int* count, int flags, void* stream)
 {
     if (!m || !f || !T || !dx || !dy || !cost || !si || !sj || !err || !count) return fail(UMPA_HIP_E_ARG, "grid: basins: null argument");
     if (K < 1 || K > UMPA_GRID_MAX_BASINS)
@@ -218,6 +364,7 @@ UMPA_GRID_API int umpa_grid_basins(umpa_hip_model* m, int start0, int step0, int
         return fail(UMPA_HIP_E_ARG, "grid: basins takes UMPA_HIP_F_DEVICE_IO, UMPA_HIP_F_USE_STAGED and no other flag");
     const int staged = flags & UMPA_HIP_F_USE_STAGED;
     GridJob J;
+    J.b = b;
     J.basins = true;
     J.B.K = K;
     J.want_df = df != nullptr;
@@ -254,10 +401,10 @@ UMPA_GRID_API int umpa_grid_basins(umpa_hip_model* m, int start0, int step0, int
     return rc;
 }
 
-UMPA_GRID_API int umpa_grid_track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
-                                  const double* prior_i, const double* prior_j, int mode, double lam, double radius,
-                                  double* f, double* T, double* dx, double* dy, double* cost, double* df,
-                                  int* si, int* sj, int* err, double* cost0, int* count, int* found, int flags, void* stream)
+int track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+          const double* prior_i, const double* prior_j, int mode, double lam, double radius,
+          double* f, double* T, double* dx, double* dy, double* cost, double* df,
+          int* si, int* sj, int* err, double* cost0, int* count, int* found, int flags, void* stream)
 {
     if (!m || !prior_i || !prior_j || !f || !T || !dx || !dy || !cost || !si || !sj || !err || !cost0 || !count || !found)
         return fail(UMPA_HIP_E_ARG, "grid: track: null argument");
@@ -270,6 +417,7 @@ UMPA_GRID_API int umpa_grid_track(umpa_hip_model* m, int start0, int step0, int 
         return fail(UMPA_HIP_E_ARG, "grid: track takes UMPA_HIP_F_DEVICE_IO, UMPA_HIP_F_USE_STAGED and no other flag");
     const int staged = flags & UMPA_HIP_F_USE_STAGED;
     GridJob J;
+    J.b = b;
     J.track = true;
     J.want_df = df != nullptr;
     J.K.mode = mode;
@@ -310,4 +458,83 @@ UMPA_GRID_API int umpa_grid_track(umpa_hip_model* m, int start0, int step0, int 
     (void)hipFree(J.block);
     if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the track maps: %s", hipGetErrorString(e));
     return rc;
+}
+
+// `b` outside 0 .. UMPA_GRID_MAX_WIDEN
+int bad_widen(int b) { return fail(UMPA_HIP_E_ARG, "grid: widen: the half-width b must be 0 to %d, not %d", UMPA_GRID_MAX_WIDEN, b); }
+
+} // namespace
+
+UMPA_GRID_API const char* umpa_grid_last_error(void) { return g_err.c_str(); }
+
+UMPA_GRID_API int umpa_grid_match_region(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                         double* values, int nparam, double* uv, int* err,
+                                         const double* covermap, double cover_threshold,
+                                         double* dbg_d, double* dbg_a, int* dbg_ncalls, int flags, void* stream)
+{
+    return match_region(m, start0, step0, N0, start1, step1, N1, 0, values, nparam, uv, err, covermap, cover_threshold,
+                        dbg_d, dbg_a, dbg_ncalls, flags, stream);
+}
+
+UMPA_GRID_API int umpa_grid_cost_volume(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                        double* cost, double* T, double* df, int flags, void* stream)
+{
+    return cost_volume(m, start0, step0, N0, start1, step1, N1, 0, cost, T, df, flags, stream);
+}
+
+UMPA_GRID_API int umpa_grid_basins(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int K,
+                                   double* f, double* T, double* dx, double* dy, double* cost, double* df,
+                                   int* si, int* sj, int* err, int* count, int flags, void* stream)
+{
+    return basins(m, start0, step0, N0, start1, step1, N1, 0, K, f, T, dx, dy, cost, df, si, sj, err, count, flags, stream);
+}
+
+UMPA_GRID_API int umpa_grid_track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                  const double* prior_i, const double* prior_j, int mode, double lam, double radius,
+                                  double* f, double* T, double* dx, double* dy, double* cost, double* df,
+                                  int* si, int* sj, int* err, double* cost0, int* count, int* found, int flags, void* stream)
+{
+    return track(m, start0, step0, N0, start1, step1, N1, 0, prior_i, prior_j, mode, lam, radius,
+                 f, T, dx, dy, cost, df, si, sj, err, cost0, count, found, flags, stream);
+}
+
+// Window widening: the NULL check of the sibling, the range of `b`, then the sibling's checks in their order.
+UMPA_GRID_API int umpa_grid_wide_match_region(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+                                              double* values, int nparam, double* uv, int* err,
+                                              const double* covermap, double cover_threshold,
+                                              double* dbg_d, double* dbg_a, int* dbg_ncalls, int flags, void* stream)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "grid: null model");
+    if (b < 0 || b > UMPA_GRID_MAX_WIDEN) return bad_widen(b);
+    return match_region(m, start0, step0, N0, start1, step1, N1, b, values, nparam, uv, err, covermap, cover_threshold,
+                        dbg_d, dbg_a, dbg_ncalls, flags, stream);
+}
+
+UMPA_GRID_API int umpa_grid_wide_cost_volume(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+                                             double* cost, double* T, double* df, int flags, void* stream)
+{
+    if (!m || !cost) return fail(UMPA_HIP_E_ARG, "grid: null argument");
+    if (b < 0 || b > UMPA_GRID_MAX_WIDEN) return bad_widen(b);
+    return cost_volume(m, start0, step0, N0, start1, step1, N1, b, cost, T, df, flags, stream);
+}
+
+UMPA_GRID_API int umpa_grid_wide_basins(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int b, int K,
+                                        double* f, double* T, double* dx, double* dy, double* cost, double* df,
+                                        int* si, int* sj, int* err, int* count, int flags, void* stream)
+{
+    if (!m || !f || !T || !dx || !dy || !cost || !si || !sj || !err || !count) return fail(UMPA_HIP_E_ARG, "grid: basins: null argument");
+    if (b < 0 || b > UMPA_GRID_MAX_WIDEN) return bad_widen(b);
+    return basins(m, start0, step0, N0, start1, step1, N1, b, K, f, T, dx, dy, cost, df, si, sj, err, count, flags, stream);
+}
+
+UMPA_GRID_API int umpa_grid_wide_track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1, int b,
+                                       const double* prior_i, const double* prior_j, int mode, double lam, double radius,
+                                       double* f, double* T, double* dx, double* dy, double* cost, double* df,
+                                       int* si, int* sj, int* err, double* cost0, int* count, int* found, int flags, void* stream)
+{
+    if (!m || !prior_i || !prior_j || !f || !T || !dx || !dy || !cost || !si || !sj || !err || !cost0 || !count || !found)
+        return fail(UMPA_HIP_E_ARG, "grid: track: null argument");
+    if (b < 0 || b > UMPA_GRID_MAX_WIDEN) return bad_widen(b);
+    return track(m, start0, step0, N0, start1, step1, N1, b, prior_i, prior_j, mode, lam, radius,
+                 f, T, dx, dy, cost, df, si, sj, err, cost0, count, found, flags, stream);
 }

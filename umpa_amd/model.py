@@ -125,6 +125,67 @@ def resolve_region(extent, ROI, step, current):
     return s0, s1, N0, N1
 
 
+def check_widen(widen, search='grid'):
+    """``widen`` as the grid consumers take it (``include/umpa_grid.h``, window widening): an integer half-width from 0 to
+    ``_lib.GRID_MAX_WIDEN``; more than 0 only beside ``search='grid'``.  Returns it as an ``int``."""
+    if isinstance(widen, (bool, np.bool_)) or not isinstance(widen, (int, np.integer)) or not 0 <= widen <= _lib.GRID_MAX_WIDEN:
+        raise ValueError("widen must be an integer from 0 to %d, not %r" % (_lib.GRID_MAX_WIDEN, widen))
+    if widen and search != 'grid':
+        raise ValueError("widen > 0 needs search='grid': the walk reads the cost under the model's own window")
+    return int(widen)
+
+
+def _widen_axis(E, s, N, b):
+    """One axis of ``widen_region``: ``(native start, native count, first kept native index, kept count)``."""
+    start, step = s[0], s[2]
+    last = start + step * (N - 1)
+    m = -(-b // step)                                               # grid points that cover b dense pixels
+    lo, hi = min(m, start // step), min(m, (E - 1 - last) // step)
+    n_start, n_last = start - step * lo, last + step * hi
+    klo = max(0, -((start - n_start - b) // step))                  # the first k with start + step k - b >= n_start
+    khi = min(N - 1, (n_last - b - start) // step)
+    return n_start, N + lo + hi, klo + lo, khi - klo + 1
+
+
+def widen_region(extent, s0, s1, N0, N1, b):
+    """The region a widened call (half-width ``b``) computes for the requested one, and what of it is kept.
+
+    The library gives NaN costs to the pixels within ``b`` dense pixels of the border of the region it is called on.  So the
+    call is made on the requested grid grown by ``ceil(b / step)`` grid points on every side, or by as many as stay inside
+    ``extent``, and the result is cropped to the requested pixels whose ``(2b + 1)^2`` block lies inside the grown
+    region's dense grid: with unit steps, all whose widened window fits the extent.
+
+    Returns ``(native, crop, region)``: ``native = (s0, s1, N0, N1)`` for the library, ``crop`` the two slices of its maps
+    that are kept, ``region`` the kept pixels as two ``(start, end, step)`` triples."""
+    a0 = _widen_axis(extent[0], s0, N0, b)
+    a1 = _widen_axis(extent[1], s1, N1, b)
+    if a0[3] < 1 or a1[3] < 1:
+        raise RuntimeError("widen=%d: no pixel of the region %s keeps its widened window inside the extent %s"
+                           % (b, (s0, s1), tuple(extent)))
+    native = ((a0[0], a0[0] + s0[2] * (a0[1] - 1) + 1, s0[2]), (a1[0], a1[0] + s1[2] * (a1[1] - 1) + 1, s1[2]), a0[1], a1[1])
+    crop = (slice(a0[2], a0[2] + a0[3]), slice(a1[2], a1[2] + a1[3]))
+    first0, first1 = a0[0] + s0[2] * a0[2], a1[0] + s1[2] * a1[2]
+    region = ((first0, first0 + s0[2] * (a0[3] - 1) + 1, s0[2]), (first1, first1 + s1[2] * (a1[3] - 1) + 1, s1[2]))
+    return native, crop, region
+
+
+def _grown(p, shape, crop):
+    """A prior plane of the kept region inside a NaN plane of the grown one (``widen_region``), on the prior's side."""
+    if hasattr(p, "data_ptr"):
+        import torch
+        full = torch.full(tuple(shape), float("nan"), dtype=p.dtype, device=p.device)
+    else:
+        full = np.full(shape, np.nan, dtype=NPDOUBLE)
+    full[tuple(crop)] = p
+    return full
+
+
+def _cropped(a, crop):
+    """The kept pixels (last two axes) of a map of a widened call, contiguous: a numpy array or a HIP tensor."""
+    v = a[(Ellipsis,) + tuple(crop)]
+    return v.contiguous() if hasattr(v, "data_ptr") else np.ascontiguousarray(v)
+
+
 class UMPAModelBase:
     """Mirror of ``UMPAModelBase`` (``model.pyx:116-755``)."""
 
@@ -348,9 +409,10 @@ class UMPAModelBase:
 
     # -- the match loop (model.pyx:334-497)
     def _match(self, step=None, input_values=None, dxdy=None, ROI=None,
-               num_threads=None, quiet=False, search='walk'):
+               num_threads=None, quiet=False, search='walk', widen=0):
         if search not in ('walk', 'grid'):
             raise ValueError("search must be 'walk' or 'grid', not %r" % (search,))
+        widen = check_widen(widen, search)
         grid = search == 'grid'
         if grid:
             self._grid_check("search='grid'")
@@ -365,6 +427,10 @@ class UMPAModelBase:
                 print("Using HIP device %d" % self._device)
         self._set_ROI(self._convert_ROI_slice(ROI, step))                # remembered before it is checked, as in the reference
         s0, s1, N0, N1 = self._region()
+        wide = None
+        if widen:                                                   # the call is made on a grown region and cropped below
+            wide = widen_region(self._calculate_extent(), s0, s1, N0, N1, widen)
+            s0, s1, N0, N1 = wide[0]
         sh = (N0, N1)
         shp = (N0, N1, self.Nparam)
         planar = False
@@ -426,12 +492,25 @@ class UMPAModelBase:
             args += [int(num_threads) if num_threads else max(1, self._lib.max_threads())]
         if grid:
             try:
-                _lib.grid().check(_lib.grid().match_region(*args), "grid match_region")
+                if wide:
+                    _lib.grid().check(_lib.grid().wide_match_region(*(args[:7] + [widen] + args[7:])), "grid wide_match_region")
+                else:
+                    _lib.grid().check(_lib.grid().match_region(*args), "grid match_region")
             except _lib.NativeError as e:
                 raise RuntimeError("search='grid': %s" % e) from None
         else:
             self._lib.check(self._lib.match_region(*args), "match_region")
 
+        if wide:                                                    # (planar on this path: the maps' last axes are the pixels)
+            r0, r1 = wide[1]
+            if planar:
+                values = _cropped(values, wide[1])
+            else:
+                values = np.ascontiguousarray(values[r0, r1])
+            err = _cropped(err, wide[1])
+            dd, da = [None if a is None else np.ascontiguousarray(a[r0, r1]) for a in (dd, da)]
+            dn = None if dn is None else _cropped(dn, wide[1])
+            result['region'] = wide[2]
         result['values'] = values
         result['_planar'] = planar
         result['err'] = err
@@ -460,48 +539,72 @@ class UMPAModelBase:
         if why:
             raise RuntimeError("%s (grid search / cost volume): %s" % (what, why))
 
-    def _grid_cost_volume(self, ROI, step, alloc):
+    def _grid_cost_volume(self, ROI, step, alloc, widen=0):
         """The one ``umpa_grid_cost_volume`` call.  ``alloc(U, N0, N1)`` gives the output arrays once the model and the region
         have passed, as a dictionary of ``cost`` and, where wanted, ``T`` and ``df``: host arrays, or HIP tensors that the
         library fills on the current stream.  This call is given the staged stack, so it spends the one-shot flag.
-        Returns ``(s0, s1, arrays)``."""
+        Returns ``(s0, s1, arrays)``.  ``widen`` > 0 (window widening): ``alloc`` is asked for the grown region's arrays,
+        and what comes back is the kept region (``widen_region``) and contiguous copies of its part of the arrays."""
         self._grid_check("cost_volume")
+        widen = check_widen(widen)
         s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
+        wide = widen_region(self._calculate_extent(), s0, s1, N0, N1, widen) if widen else None
+        if wide:
+            s0, s1, N0, N1 = wide[0]
         out = alloc(2 * self._max_shift - 1, N0, N1)
         _, flags, stream = _lib.Side(out['cost'], device=self._device).tail(self._staged_flag())
+        region = (self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1)
+        tail = [_lib.Side.ptr(out.get(k)) for k in ('cost', 'T', 'df')] + [flags, stream]
         try:
-            _lib.grid().check(_lib.grid().cost_volume(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1,
-                                                      *[_lib.Side.ptr(out.get(k)) for k in ('cost', 'T', 'df')], flags, stream), "grid cost_volume")
+            if wide:
+                _lib.grid().check(_lib.grid().wide_cost_volume(*region, widen, *tail), "grid wide_cost_volume")
+            else:
+                _lib.grid().check(_lib.grid().cost_volume(*region, *tail), "grid cost_volume")
         except _lib.NativeError as e:
             raise RuntimeError("cost_volume: %s" % e) from None
+        if wide:
+            return wide[2][0], wide[2][1], {k: _cropped(v, wide[1]) for k, v in out.items()}
         return s0, s1, out
 
-    def _cost_volume(self, ROI=None, step=None, with_fit=False):
+    def _cost_volume(self, ROI=None, step=None, with_fit=False, widen=0):
         keys = ['cost'] + (['T'] + (['df'] if self._kind == KIND_DF else []) if with_fit else [])
-        return self._grid_cost_volume(ROI, step, lambda U, N0, N1: {k: np.empty((U, U, N0, N1), dtype=NPDOUBLE) for k in keys})[2]
+        s0, s1, out = self._grid_cost_volume(ROI, step, lambda U, N0, N1: {k: np.empty((U, U, N0, N1), dtype=NPDOUBLE) for k in keys}, widen)
+        if widen:
+            out['region'] = (s0, s1)
+        return out
 
-    def _grid_basins(self, k, ROI, step, alloc):
+    def _grid_basins(self, k, ROI, step, alloc, widen=0):
         """The one ``umpa_grid_basins`` call.  ``alloc(k, N0, N1)`` gives the output arrays once the model, ``k`` and the region
         have passed: a dictionary of ``f``, ``T``, ``dx``, ``dy``, ``cost`` (and ``df``: dark-field model) as float64
         ``[k, N0, N1]``, ``si``, ``sj``, ``err`` as int32 ``[k, N0, N1]`` and ``count`` as int32 ``[N0, N1]`` -- host arrays, or
         HIP tensors that the library fills on the current stream.  This call is given the staged stack, so it spends the
-        one-shot flag.  Returns ``(s0, s1, arrays)``."""
+        one-shot flag.  Returns ``(s0, s1, arrays)``.  ``widen`` as for ``_grid_cost_volume``."""
         self._grid_check("basins")
+        widen = check_widen(widen)
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not _lib.GRID_MIN_K <= k <= _lib.GRID_MAX_K:
             raise ValueError("basins: k must be an integer from %d to %d, not %r" % (_lib.GRID_MIN_K, _lib.GRID_MAX_K, k))
         k = int(k)
         s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
+        wide = widen_region(self._calculate_extent(), s0, s1, N0, N1, widen) if widen else None
+        if wide:
+            s0, s1, N0, N1 = wide[0]
         out = alloc(k, N0, N1)
         _, flags, stream = _lib.Side(out['cost'], device=self._device).tail(self._staged_flag())
         names = ('f', 'T', 'dx', 'dy', 'cost', 'df', 'si', 'sj', 'err', 'count')
+        region = (self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1)
+        tail = [k] + [_lib.Side.ptr(out.get(n)) for n in names] + [flags, stream]
         try:
-            _lib.grid().check(_lib.grid().basins(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1, k,
-                                                 *[_lib.Side.ptr(out.get(n)) for n in names], flags, stream), "grid basins")
+            if wide:
+                _lib.grid().check(_lib.grid().wide_basins(*region, widen, *tail), "grid wide_basins")
+            else:
+                _lib.grid().check(_lib.grid().basins(*region, *tail), "grid basins")
         except _lib.NativeError as e:
             raise RuntimeError("basins: %s" % e) from None
+        if wide:
+            return wide[2][0], wide[2][1], {n: _cropped(v, wide[1]) for n, v in out.items()}
         return s0, s1, out
 
-    def _basins(self, k=4, ROI=None, step=None):
+    def _basins(self, k=4, ROI=None, step=None, widen=0):
         dbl = ['f', 'T', 'dx', 'dy', 'cost'] + (['df'] if self._kind == KIND_DF else [])
 
         def alloc(k, N0, N1):                                      # page-locked, as the result maps of match(): downloaded at PCIe rate
@@ -510,33 +613,48 @@ class UMPAModelBase:
             out['count'] = _lib.pinned_empty((N0, N1), np.int32)
             return out
 
-        out = self._grid_basins(k, ROI, step, alloc)[2]
+        s0, s1, out = self._grid_basins(k, ROI, step, alloc, widen)
         out['shift'] = np.stack([out.pop('si'), out.pop('sj')], axis=1)
+        if widen:
+            out['region'] = (s0, s1)
         return out
 
-    def _grid_track(self, prior, mode, lam, radius, ROI, step, alloc):
+    def _grid_track(self, prior, mode, lam, radius, ROI, step, alloc, widen=0):
         """The one ``umpa_grid_track`` call.  ``prior(N0, N1)`` gives the two prior planes (row shift, column shift) and
         ``alloc(N0, N1)`` the output arrays once the model and the region have passed: float64 ``[N0, N1]`` each, the
         outputs a dictionary of ``f``, ``T``, ``dx``, ``dy``, ``cost``, ``cost0`` (and ``df``: dark-field model) as float64 and
         ``si``, ``sj``, ``err``, ``count``, ``found`` as int32 -- all host arrays, or all HIP tensors that the library reads and
         fills on the current stream.  This call is given the staged stack, so it spends the one-shot flag.
-        Returns ``(s0, s1, arrays)``."""
+        Returns ``(s0, s1, arrays)``.  ``widen`` as for ``_grid_cost_volume``; ``prior`` is asked for planes of the KEPT
+        region, which go into NaN planes of the grown one (its other pixels have no basin anyway)."""
         self._grid_check("track")
+        widen = check_widen(widen)
         s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
-        pi, pj = prior(N0, N1)
+        wide = widen_region(self._calculate_extent(), s0, s1, N0, N1, widen) if widen else None
+        if wide:
+            s0, s1, N0, N1 = wide[0]
+            kept = prior(wide[1][0].stop - wide[1][0].start, wide[1][1].stop - wide[1][1].start)
+            pi, pj = [_grown(p, (N0, N1), wide[1]) for p in kept]
+        else:
+            pi, pj = prior(N0, N1)
         out = alloc(N0, N1)
         _, flags, stream = _lib.Side(pi, pj, *out.values(), device=self._device,
                                      mixed="track: the priors and the outputs must be all host arrays or all HIP tensors").tail(self._staged_flag())
         names = ('f', 'T', 'dx', 'dy', 'cost', 'df', 'si', 'sj', 'err', 'cost0', 'count', 'found')
+        region = (self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1)
+        tail = [_lib.Side.ptr(pi), _lib.Side.ptr(pj), int(mode), float(lam), float(radius)] + [_lib.Side.ptr(out.get(n)) for n in names] + [flags, stream]
         try:
-            _lib.grid().check(_lib.grid().track(self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1,
-                                                _lib.Side.ptr(pi), _lib.Side.ptr(pj), int(mode), float(lam), float(radius),
-                                                *[_lib.Side.ptr(out.get(n)) for n in names], flags, stream), "grid track")
+            if wide:
+                _lib.grid().check(_lib.grid().wide_track(*region, widen, *tail), "grid wide_track")
+            else:
+                _lib.grid().check(_lib.grid().track(*region, *tail), "grid track")
         except _lib.NativeError as e:
             raise RuntimeError("track: %s" % e) from None
+        if wide:
+            return wide[2][0], wide[2][1], {n: _cropped(v, wide[1]) for n, v in out.items()}
         return s0, s1, out
 
-    def _track(self, prior_dx, prior_dy, lam=None, radius=None, ROI=None, step=None):
+    def _track(self, prior_dx, prior_dy, lam=None, radius=None, ROI=None, step=None, widen=0):
         self._grid_check("track")
         number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
         if lam is not None and not (number(lam) and 0.0 <= float(lam) < np.inf):
@@ -584,7 +702,9 @@ class UMPAModelBase:
             out.update({n: _lib.pinned_empty((N0, N1), np.int32) for n in ints})
             return out
 
-        out = self._grid_track(prior, mode, 0.0 if lam is None else lam, -1.0 if radius is None else radius, ROI, step, alloc)[2]
+        s0, s1, out = self._grid_track(prior, mode, 0.0 if lam is None else lam, -1.0 if radius is None else radius, ROI, step, alloc, widen)
+        if widen:
+            out['region'] = (s0, s1)
         si, sj, err = out.pop('si'), out.pop('sj'), out.pop('err')
         if dev is not None:
             import torch
@@ -799,14 +919,21 @@ class _UMPAModelPlain(UMPAModelBase):
                                        _lib._ptr(values, _lib._dp)), "cost")
         return tuple(values)
 
-    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk'):
+    def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk', widen=0):
         """``search='walk'`` (default): the reference's minimiser.  ``search='grid'`` (extension): the global minimum over
         all ``(2 max_shift - 1)^2`` integer shifts, then the same sub-pixel step around it (``include/umpa_grid.h``);
-        plain models only (no masks, no ``pos_list``), no ``dxdy``."""
-        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet, search=search)
+        plain models only (no masks, no ``pos_list``), no ``dxdy``.
+
+        ``widen=b`` (1 to 8, with ``search='grid'``; also on ``cost_volume``, ``basins`` and ``track``): window widening
+        (``include/umpa_grid.h``).  The shift table and the maps are averaged over the ``(2b + 1)^2`` dense pixels around each
+        pixel before the search, which is the search of a model whose window is ``umpa_amd.widen.window(Nw, b)``, of
+        half-width ``Nw + b`` -- on this model, without a new upload.  The result covers the requested pixels whose widened
+        window fits the extent (``umpa_amd.widen.valid_region``) and has one more key, ``region``: the covered pixels as a
+        row and a column ``(start, end, step)`` triple.  ``widen=0`` is the call without the keyword."""
+        result = self._match(step=step, dxdy=dxdy, ROI=ROI, num_threads=num_threads, quiet=quiet, search=search, widen=widen)
         return self._unpack(result, self._kind == KIND_DF)
 
-    def cost_volume(self, ROI=None, step=None, with_fit=False):
+    def cost_volume(self, ROI=None, step=None, with_fit=False, widen=0):
         """The cost of EVERY integer shift of the search box at every pixel of the region (extension; the
         reference offers ``utils.get_cost``, a Python loop over ``cost()`` for one pixel): a dictionary with
         ``cost[U, U, N0, N1]``, ``U = 2 max_shift - 1``, where ``cost[si + max_shift - 1, sj + max_shift - 1, xi, xj]``
@@ -819,10 +946,10 @@ class _UMPAModelPlain(UMPAModelBase):
         ``max_shift=5`` -- so a ``ROI`` of the rows or the patch in question is the normal use.
 
         Models the plain tiled path takes whole only (no masks, no ``pos_list``, steps and search ranges within its
-        limits); anything else raises ``RuntimeError``."""
-        return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit)
+        limits); anything else raises ``RuntimeError``.  ``widen``: as for ``match()``."""
+        return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit, widen=widen)
 
-    def basins(self, k=4, ROI=None, step=None):
+    def basins(self, k=4, ROI=None, step=None, widen=0):
         """Per pixel, the ``k`` lowest local minima ("basins") of the cost over the search box (extension;
         ``include/umpa_grid.h`` has the definition): a shift is a basin iff its cost is below ``+Inf`` and none of its up
         to eight neighbours inside the box has a lower cost, or an equal one earlier in scan order (rows first, then
@@ -840,10 +967,10 @@ class _UMPAModelPlain(UMPAModelBase):
 
         ``k``: 1 to 8.  ``ROI`` / ``step`` as for ``cost_volume()``; the model's own ROI is not changed; a stack uploaded by
         ``stage_sample`` is adopted as by ``cost_volume()``.  Models ``cost_volume()`` takes only; anything else raises
-        ``RuntimeError``.  ``umpa_amd.basins`` has helpers that pick among the ranks."""
-        return self._basins(k=k, ROI=ROI, step=step)
+        ``RuntimeError``.  ``umpa_amd.basins`` has helpers that pick among the ranks.  ``widen``: as for ``match()``."""
+        return self._basins(k=k, ROI=ROI, step=step, widen=widen)
 
-    def track(self, prior_dx, prior_dy, lam=None, radius=None, ROI=None, step=None):
+    def track(self, prior_dx, prior_dy, lam=None, radius=None, ROI=None, step=None, widen=0):
         """Tracked search (extension; ``include/umpa_grid.h``: ``umpa_grid_track`` has the definition): per pixel, among ALL
         basins of the cost over the search box -- not only the eight ``basins()`` can keep -- the one a prior shift
         ``(prior_dy rows, prior_dx columns)`` selects, finished like ``match(search='grid')`` finishes its minimum.  One pass on
@@ -865,8 +992,9 @@ class _UMPAModelPlain(UMPAModelBase):
         ``err`` is 1 where the sub-pixel fit succeeded and 0 otherwise, as ``match()`` has it; ``found == 0`` tells a pixel
         without an admissible basin (zeros) from one whose 4x4 neighbourhood leaves the search range.
 
-        ``ROI`` / ``step``, the staged stack and the admitted models as for ``basins()``."""
-        return self._track(prior_dx, prior_dy, lam=lam, radius=radius, ROI=ROI, step=step)
+        ``ROI`` / ``step``, the staged stack and the admitted models as for ``basins()``.  ``widen``: as for ``match()``; the
+        priors then have the shape of the result (the kept region) or are scalars."""
+        return self._track(prior_dx, prior_dy, lam=lam, radius=radius, ROI=ROI, step=step, widen=widen)
 
     def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
         """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
