@@ -13,7 +13,9 @@
  *   umpa_grid_track         per pixel, among ALL its basins, the one nearest a prior shift (or the best under cost plus a
  *                           distance penalty), finished like a kept basin: one set of maps, the prior may live on the device.
  *   umpa_grid_wide_<name>   each of the four on a shift table and maps box-averaged over the (2b + 1)^2 dense pixels around a
- *                           pixel: the same search under a window b pixels wider, on the same model ("window widening").
+ *                           pixel: the same search under a window b pixels wider, on the same model ("window widening");
+ *   umpa_grid_levels_track  umpa_grid_wide_track at up to four half-widths from one pass over the table, each level the prior
+ *                           of the next, and per pixel the narrowest level that agrees with the wider ones ("scale space").
  *
  * All work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
  * one shape at position (0, 0), steps and search ranges within that path's limits.  Anything else fails with
@@ -196,6 +198,49 @@ int umpa_grid_wide_track(umpa_hip_model *m, int start0, int step0, int N0, int s
                          const double *prior_i, const double *prior_j, int mode, double lam, double radius,
                          double *f, double *T, double *dx, double *dy, double *cost, double *df,
                          int *si, int *sj, int *err, double *cost0, int *count, int *found, int flags, void *stream);
+
+/* Scale-space search: umpa_grid_wide_track at several half-widths from one table pass, and the level to trust per pixel.
+ *
+ * Levels.  L levels, 1 <= L <= UMPA_GRID_MAX_LEVELS, of half-widths b[0] > b[1] > ... > b[L-1].  The widened half-widths
+ *   come from {1, 2, 4, 8}, at most three of them; an optional final 0 is the model's own window.  Any other list is
+ *   UMPA_HIP_E_ARG, and the text names the list.
+ * Level 0 is umpa_grid_wide_track at b[0] with a prior that is NaN at every pixel: by the rule of umpa_grid_track (a NaN prior
+ *   leaves the pixel to the data term) the grid search under the window widened by b[0], finished as a track result.
+ * Level l > 0 is umpa_grid_wide_track at b[l] on the same region, with the call's mode, lam and radius, and the prior
+ *     ok    = err == 1 && isfinite(dx) && isfinite(dy)      of level l - 1,
+ *     p_i   = ok ? dy : NaN,   p_j = ok ? dx : NaN,
+ *   which is umpa_amd.track.prior_from, expression for expression.
+ * Each level's planes -- f, T, dx, dy, cost, df, si, sj, err, cost0, count, found, [L][N0][N1] each -- are exactly what
+ *   the sibling writes for that region, b and prior, the NaN rules of window widening included: level l holds found = 0,
+ *   err = -1, count = 0 and zeros at the pixels whose (2 b[l] + 1)^2 block leaves the region's dense grid.
+ * Selection.  tol: L doubles, each >= 0 or +Inf (NaN and negative values are UMPA_HIP_E_ARG); NULL: all +Inf.  With
+ *     ok_l  = err_l == 1 && isfinite(dx_l) && isfinite(dy_l),
+ *   level l is CONSISTENT iff ok_l and, for every wider level m < l with ok_m,
+ *     fabs(dx_l - dx_m) <= tol[m]  &&  fabs(dy_l - dy_m) <= tol[m]
+ *   (one rounded subtraction, fabs, one comparison of doubles each).  level(p) is the largest consistent l, -1 where no
+ *   level is ok: the narrowest window that still agrees with every wider one that matched (Lepski's rule).  tol[L-1] is
+ *   read by nothing.  The selected planes, the same twelve as [N0][N1], are copies of level level(p)'s values; at -1 they
+ *   are copies of level L - 1's, which hold the sibling's values for a pixel without a match.  `level` is level(p) and
+ *   `halfwidth` b[level(p)], or -1, as ints.  The thirteen selected arrays (df aside) are all given or all NULL.
+ *
+ * The model and the region as for umpa_grid_wide_track.  Host arrays, or device arrays with UMPA_HIP_F_DEVICE_IO (the call
+ * then only enqueues work on `stream`); UMPA_HIP_F_USE_STAGED as for umpa_grid_cost_volume.  df and sel_df may be NULL
+ * (dark-field model only).  Checked in this order before anything touches a device, each UMPA_HIP_E_ARG: a NULL model, list or
+ * per-level array (other than df); L; the list b; tol; a selected group that is given in part; then umpa_grid_wide_track's
+ * checks with its texts (mode, lam, radius, flags).
+ * One pass.  The shift table and the maps are computed once; a row chunk's table is pooled to every widened level in one
+ * read of its raw rows, and all levels lag by b[0] rows, so that a level's prior is finished when its rows are searched.
+ * The workspace (up to three pooled chunk tables, the carry of 2 b[0] raw rows, the pooled maps per level, two prior planes)
+ * comes from the stream-ordered allocator as for window widening.  The output is the same bit for bit from run to run, for
+ * host and device arrays and under any row chunking. */
+#define UMPA_GRID_MAX_LEVELS 4
+int umpa_grid_levels_track(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
+                           int L, const int *b, int mode, double lam, double radius, const double *tol,
+                           double *f, double *T, double *dx, double *dy, double *cost, double *df,
+                           int *si, int *sj, int *err, double *cost0, int *count, int *found,
+                           double *sel_f, double *sel_T, double *sel_dx, double *sel_dy, double *sel_cost, double *sel_df,
+                           int *sel_si, int *sel_sj, int *sel_err, double *sel_cost0, int *sel_count, int *sel_found,
+                           int *level, int *halfwidth, int flags, void *stream);
 
 const char *umpa_grid_last_error(void);
 

@@ -23,6 +23,8 @@ volume on ``libumpa_smooth.so`` and start the ordinary walk from it.
 (``umpa_amd.track``) run a step series on it, each projection's shifts being the next one's prior.
 ``widen=b`` on ``match(search='grid')``, ``cost_volume``, ``basins`` and ``track`` searches under a window ``b`` pixels wider,
 on the same model; ``umpa_amd.widen`` has that window, the region of a widened result and ``coarse_to_fine``.
+``scale_space`` (``umpa_amd.levels``) runs every widening level of that chain from one pass over the shift table and picks,
+per pixel, the narrowest level that agrees with every wider one; ``select_levels`` states the rule in numpy.
 """
 from . import model
 from . import align
@@ -41,6 +43,8 @@ from . import basins
 from . import track
 from .track import Tracker, prior_from
 from . import widen
+from . import levels
+from .levels import scale_space, select_levels
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
            "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration",
@@ -49,4 +53,5 @@ __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAMo
            "sigma", "uncertainty", "Uncertainty",
            "basins",
            "track", "Tracker", "prior_from",
-           "widen"]
+           "widen",
+           "levels", "scale_space", "select_levels"]

@@ -170,6 +170,11 @@ _GRID_ABI = {
 GRID_MAX_WIDEN = 8                                               # UMPA_GRID_MAX_WIDEN
 for _name in ("match_region", "cost_volume", "basins", "track"):
     _GRID_ABI["wide_" + _name] = (_int, _GRID_ABI[_name][1][:7] + [_int] + _GRID_ABI[_name][1][7:])
+# umpa_grid_levels_track: the model and the region, the level list, track's mode, lam and radius, tol, the twelve per-level
+# arrays, the twelve selected ones, level and halfwidth
+GRID_MAX_LEVELS = 4                                              # UMPA_GRID_MAX_LEVELS
+GRID_LEVEL_WIDTHS = (1, 2, 4, 8)
+_GRID_ABI["levels_track"] = (_int, [_vp] + [_int] * 6 + [_int, _vp, _int, _dbl, _dbl, _vp] + [_vp] * 26 + [_int, _vp])
 GRID_SYMBOLS = list(_GRID_ABI)
 
 # include/umpa_unwarp.h: detector distortion correction, stand-alone and fused into stage_sample of models of libumpa_hip.so

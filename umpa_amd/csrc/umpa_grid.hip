@@ -1,11 +1,12 @@
 // umpa_grid.hip -- libumpa_grid.so: exhaustive grid search and the cost volume (include/umpa_grid.h).  gfx950 only.
 //
 // A second library, built from the headers of libumpa_hip.so by the same build: it holds the kernel families of
-// umpa_grid_kernels.h, umpa_basins_kernels.h, umpa_track_kernels.h and umpa_widen_kernels.h and no other feature code.  A call sets itself as the model's table
+// umpa_grid_kernels.h, umpa_basins_kernels.h, umpa_track_kernels.h, umpa_widen_kernels.h and umpa_levels_kernels.h and no other feature code.  A call sets itself as the model's table
 // consumer (umpa_hipx.h), runs umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
 #include <hip/hip_runtime.h>
 #include <cstring>
+#include <string>
 
 #include "../../include/umpa_grid.h"
 #include "umpa_host.h"
@@ -14,6 +15,7 @@
 #include "umpa_basins_kernels.h"
 #include "umpa_track_kernels.h"
 #include "umpa_widen_kernels.h"
+#include "umpa_levels_kernels.h"
 
 using namespace umpa;
 
@@ -59,6 +61,18 @@ struct GridJob {
     RegionArgs mh = {};               // the caller's host arrays (values, err, cover, dbg_*) and nparam
     void* mblock = nullptr;
     RegionArgs md = {};               // their device twins
+    // umpa_grid_levels_track (L > 0): `track` per level on one table pass.  lb[0] is the lag of every level; the workspace
+    // holds a pooled table and a set of pooled maps per widened level (pools, lmaps), the carry and two prior planes.
+    // lev / sel: the caller's device arrays, or their places in `block` (host arrays)
+    int L = 0, lb[UMPA_LEVELS_MAX] = {0, 0, 0, 0};
+    double ltol[UMPA_LEVELS_MAX] = {0.0, 0.0, 0.0, 0.0};
+    double* pools[3] = {nullptr, nullptr, nullptr};
+    double* lmaps[3] = {nullptr, nullptr, nullptr};
+    double* prior = nullptr;
+    LevelsPlanes lev = {}, sel = {};
+    int* sel_level = nullptr;
+    int* sel_hw = nullptr;
+    bool want_sel = false;
 };
 
 // the block of umpa_grid_wide_match_region's host path: values, dbg_d, dbg_a, cover (doubles), then err, dbg_n (ints)
@@ -121,6 +135,44 @@ void launch(const GridJob& J, const ModelDev& dev, const Maps& M, const ReplayAr
     }
 }
 
+#define UMPA_WIDEN_HB(...) switch (b) { case 1: { constexpr int HB = 1; __VA_ARGS__; } break; case 2: { constexpr int HB = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int HB = 3; __VA_ARGS__; } break; case 4: { constexpr int HB = 4; __VA_ARGS__; } break; case 5: { constexpr int HB = 5; __VA_ARGS__; } break; \
+        case 6: { constexpr int HB = 6; __VA_ARGS__; } break; case 7: { constexpr int HB = 7; __VA_ARGS__; } break; case 8: { constexpr int HB = 8; __VA_ARGS__; } break; }
+
+// the pooled maps of half-width b (prep_maps has filled the raw ones for the whole region): zero where nothing is pooled
+// (only pixels whose table entries are NaN read there)
+hipError_t widen_maps(int b, const ModelDev& dev, const Maps& M, const RegionArgs& A, int N0d, int N1d, double* wmaps, hipStream_t s)
+{
+    const int KP = (dev.Na + 1) / 2;
+    const bool df = M.WS != nullptr;
+    const size_t plane = (size_t)M.H * M.W, nmap = (2 + (df ? 4 * (size_t)KP : 0)) * plane;
+    hipError_t e;
+    if ((e = hipMemsetAsync(wmaps, 0, nmap * sizeof(double), s)) != hipSuccess) return e;
+    WidenMapArgs a;
+    a.W = M.W; a.plane = plane;
+    a.r0 = std::max(A.org0 - (dev.ms - 1) + b, b); a.r1 = std::min(A.org0 + N0d - 1 + (dev.ms - 1) - b + 1, M.H - b);
+    a.c0 = std::max(A.org1 - (dev.ms - 1) + b, b); a.c1 = std::min(A.org1 + N1d - 1 + (dev.ms - 1) - b + 1, M.W - b);
+    if (a.r0 < a.r1 && a.c0 < a.c1) {
+        const dim3 grd((a.c1 - a.c0 + 63) / 64, (a.r1 - a.r0 + UMPA_WIDEN_SEG - 1) / UMPA_WIDEN_SEG, 2);
+        UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_map_kernel<HB, false>), grd, dim3(64), 0, s, (const void*)M.SamSq, (void*)wmaps, a))
+        if (df) {                                                     // (tiled_maps) WS and MR lie behind each other: 2 KP planes of pairs
+            const dim3 grp(grd.x, grd.y, 2 * KP);
+            UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_map_kernel<HB, true>), grp, dim3(64), 0, s, (const void*)M.WS, (void*)(wmaps + 2 * plane), a))
+        }
+    }
+    return hipGetLastError();
+}
+
+// the pooled table of the rows [g.p0, g.p1) at half-width g.b, from the chunk's table and the carry
+void widen_table(const WidenGeom& g, const double* table, const double* carry, double* pool, hipStream_t s)
+{
+    const int b = g.b;
+    const dim3 grd((g.N1q + 63) / 64, g.U2, (g.p1 - g.p0 + UMPA_WIDEN_SEG - 1) / UMPA_WIDEN_SEG);
+    if (g.strip_w > 0) { UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_table_kernel<HB, true>), grd, dim3(64), 0, s, table, carry, pool, g)) }
+    else { UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_table_kernel<HB, false>), grd, dim3(64), 0, s, table, carry, pool, g)) }
+}
+#undef UMPA_WIDEN_HB
+
 // Window widening, one row chunk: the pooled maps (first chunk; prep_maps has filled the raw ones for the whole region), the
 // pooled table of the dense rows whose block is complete (widen_rows), the carry for the next chunk.  `Mw`, `Rw`: what the
 // consumer's kernel gets in place of M and R -- the plain table layout, the output rows among the pooled ones.
@@ -138,9 +190,6 @@ hipError_t widen_chunk(GridJob& J, const ModelDev& dev, const Maps& M, const Rep
     const bool last = R.drow0 + R.drows >= g.N0d;
     if (R.drow0 != J.next_drow0 || (!last && R.drows < 2 * b)) { J.refused = "widen: the row chunks do not follow each other"; return hipErrorInvalidValue; }
     const size_t plane = (size_t)M.H * M.W, nmap = (2 + (df ? 4 * (size_t)KP : 0)) * plane;
-#define UMPA_WIDEN_HB(...) switch (b) { case 1: { constexpr int HB = 1; __VA_ARGS__; } break; case 2: { constexpr int HB = 2; __VA_ARGS__; } break; \
-        case 3: { constexpr int HB = 3; __VA_ARGS__; } break; case 4: { constexpr int HB = 4; __VA_ARGS__; } break; case 5: { constexpr int HB = 5; __VA_ARGS__; } break; \
-        case 6: { constexpr int HB = 6; __VA_ARGS__; } break; case 7: { constexpr int HB = 7; __VA_ARGS__; } break; case 8: { constexpr int HB = 8; __VA_ARGS__; } break; }
     if (!J.ws) {
         J.pool_rows = std::min(g.N0d, g.drows + b);
         if ((size_t)J.pool_rows * g.N1q >= ((size_t)1 << 32)) { J.refused = "widen: a plane of the pooled table passes the 32-bit stride of the lookups"; return hipErrorInvalidValue; }
@@ -149,28 +198,10 @@ hipError_t widen_chunk(GridJob& J, const ModelDev& dev, const Maps& M, const Rep
         if (e != hipSuccess) { J.ws = nullptr; return hipErrorOutOfMemory; }
         J.ws_stream = s;
         J.pool = (double*)J.ws; J.carry = J.pool + pool_len; J.wmaps = J.carry + carry_len;
-        // the pooled maps: zero where nothing is pooled (only pixels whose table entries are NaN read there)
-        if ((e = hipMemsetAsync(J.wmaps, 0, nmap * sizeof(double), s)) != hipSuccess) return e;
-        WidenMapArgs a;
-        a.W = M.W; a.plane = plane;
-        a.r0 = std::max(A.org0 - (dev.ms - 1) + b, b); a.r1 = std::min(A.org0 + g.N0d - 1 + (dev.ms - 1) - b + 1, M.H - b);
-        a.c0 = std::max(A.org1 - (dev.ms - 1) + b, b); a.c1 = std::min(A.org1 + g.N1d - 1 + (dev.ms - 1) - b + 1, M.W - b);
-        if (a.r0 < a.r1 && a.c0 < a.c1) {
-            const dim3 grd((a.c1 - a.c0 + 63) / 64, (a.r1 - a.r0 + UMPA_WIDEN_SEG - 1) / UMPA_WIDEN_SEG, 2);
-            UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_map_kernel<HB, false>), grd, dim3(64), 0, s, (const void*)M.SamSq, (void*)J.wmaps, a))
-            if (df) {                                                 // (tiled_maps) WS and MR lie behind each other: 2 KP planes of pairs
-                const dim3 grp(grd.x, grd.y, 2 * KP);
-                UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_map_kernel<HB, true>), grp, dim3(64), 0, s, (const void*)M.WS, (void*)(J.wmaps + 2 * plane), a))
-            }
-        }
+        if ((e = widen_maps(b, dev, M, A, g.N0d, g.N1d, J.wmaps, s)) != hipSuccess) return e;
     }
     if (g.p1 - g.p0 > J.pool_rows) { J.refused = "widen: a row chunk larger than the first"; return hipErrorInvalidValue; }
-    if (g.p1 > g.p0) {
-        const dim3 grd((g.N1q + 63) / 64, g.U2, (g.p1 - g.p0 + UMPA_WIDEN_SEG - 1) / UMPA_WIDEN_SEG);
-        if (R.strip_w > 0) { UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_table_kernel<HB, true>), grd, dim3(64), 0, s, R.table, (const double*)J.carry, J.pool, g)) }
-        else { UMPA_WIDEN_HB(hipLaunchKernelGGL((widen_table_kernel<HB, false>), grd, dim3(64), 0, s, R.table, (const double*)J.carry, J.pool, g)) }
-    }
-#undef UMPA_WIDEN_HB
+    if (g.p1 > g.p0) widen_table(g, R.table, J.carry, J.pool, s);
     if (!last) {
         const WidenCarryCopy cc = widen_carry_copy(g);
         hipLaunchKernelGGL(widen_carry_kernel, dim3((unsigned)((cc.run + 255) / 256), (unsigned)cc.nruns), dim3(256), 0, s, R.table, J.carry, cc);
@@ -187,6 +218,162 @@ hipError_t widen_chunk(GridJob& J, const ModelDev& dev, const Maps& M, const Rep
     return hipGetLastError();
 }
 
+// the consumer's kernel on the output rows R.rows of the table R, with the frame count as a template constant where
+// replay_walk's dispatch has it (tiled_match)
+hipError_t dispatch(const GridJob& J, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
+{
+    if (R.rows <= 0 || A.N1 <= 0) return hipSuccess;
+    const int kind = M.WS ? 1 : 0;
+    const bool small = (size_t)M.H * M.W * 2 * sizeof(double) < ((size_t)1 << 32);   // a pair plane (tiled_match)
+#define UMPA_GRID_NA(n) case n: launch<1, n>(J, dev, M, R, A, s); break;
+    if (kind == 1 && small && dev.Na <= UMPA_KTEMPL) {
+        switch (dev.Na) {
+            UMPA_GRID_NA(1) UMPA_GRID_NA(2) UMPA_GRID_NA(3) UMPA_GRID_NA(4) UMPA_GRID_NA(5) UMPA_GRID_NA(6)
+            UMPA_GRID_NA(7) UMPA_GRID_NA(8) UMPA_GRID_NA(9) UMPA_GRID_NA(10) UMPA_GRID_NA(11) UMPA_GRID_NA(12)
+            UMPA_GRID_NA(13) UMPA_GRID_NA(14) UMPA_GRID_NA(15) UMPA_GRID_NA(16) UMPA_GRID_NA(17) UMPA_GRID_NA(18)
+            UMPA_GRID_NA(19) UMPA_GRID_NA(20) UMPA_GRID_NA(21) UMPA_GRID_NA(22) UMPA_GRID_NA(23) UMPA_GRID_NA(24)
+        }
+    } else if (kind == 1) launch<1, 0>(J, dev, M, R, A, s);
+    else launch<0, 0>(J, dev, M, R, A, s);
+#undef UMPA_GRID_NA
+    return hipGetLastError();
+}
+
+// umpa_grid_levels_track's block (host arrays): seven planes of doubles per level and seven selected ones in the order of
+// LevelsPlanes, then five planes of ints per level, five selected ones, `level` and `halfwidth`
+void levels_carve(GridJob& J, void* block, size_t n)
+{
+    const size_t L = (size_t)J.L;
+    double* d = (double*)block;
+    double** const lv[7] = {&J.lev.f, &J.lev.T, &J.lev.dx, &J.lev.dy, &J.lev.cost, &J.lev.df, &J.lev.cost0};
+    double** const sv[7] = {&J.sel.f, &J.sel.T, &J.sel.dx, &J.sel.dy, &J.sel.cost, &J.sel.df, &J.sel.cost0};
+    for (int q = 0; q < 7; q++) { *lv[q] = d; d += L * n; }
+    for (int q = 0; q < 7; q++) { *sv[q] = d; d += n; }
+    int* i = (int*)d;
+    int** const li[5] = {&J.lev.si, &J.lev.sj, &J.lev.err, &J.lev.count, &J.lev.found};
+    int** const si[5] = {&J.sel.si, &J.sel.sj, &J.sel.err, &J.sel.count, &J.sel.found};
+    for (int q = 0; q < 5; q++) { *li[q] = i; i += L * n; }
+    for (int q = 0; q < 5; q++) { *si[q] = i; i += n; }
+    J.sel_level = i; J.sel_hw = i + n;
+    if (!J.want_df) J.lev.df = J.sel.df = nullptr;
+}
+size_t levels_bytes(int L, size_t n) { return 7 * ((size_t)L + 1) * n * sizeof(double) + (5 * ((size_t)L + 1) + 2) * n * sizeof(int); }
+
+// the multi-level pooling of the rows [g.p0, g.p1): two or three widened levels hb[0] > hb[1] (> hb[2]) from one read
+bool levels_table(const WidenGeom& g, const int* hb, int nw, const double* table, const double* carry, double* const* pools, hipStream_t s)
+{
+    const dim3 grd((g.N1q + 63) / 64, g.U2, (g.p1 - g.p0 + UMPA_WIDEN_SEG - 1) / UMPA_WIDEN_SEG);
+    const bool strip = g.strip_w > 0;
+#define UMPA_LEVELS_CASE(A, B, C) case A * 100 + B * 10 + C: \
+        if (strip) hipLaunchKernelGGL((levels_table_kernel<A, B, C, true>), grd, dim3(64), 0, s, table, carry, pools[0], pools[1], pools[2], g); \
+        else hipLaunchKernelGGL((levels_table_kernel<A, B, C, false>), grd, dim3(64), 0, s, table, carry, pools[0], pools[1], pools[2], g); \
+        return true;
+    switch (hb[0] * 100 + hb[1] * 10 + (nw > 2 ? hb[2] : 0)) {
+        UMPA_LEVELS_CASE(2, 1, 0) UMPA_LEVELS_CASE(4, 1, 0) UMPA_LEVELS_CASE(4, 2, 0)
+        UMPA_LEVELS_CASE(8, 1, 0) UMPA_LEVELS_CASE(8, 2, 0) UMPA_LEVELS_CASE(8, 4, 0)
+        UMPA_LEVELS_CASE(4, 2, 1) UMPA_LEVELS_CASE(8, 2, 1) UMPA_LEVELS_CASE(8, 4, 1) UMPA_LEVELS_CASE(8, 4, 2)
+    }
+#undef UMPA_LEVELS_CASE
+    return false;
+}
+
+// Scale-space search, one row chunk (umpa_levels_geom.h has the row arithmetic): every widened level's pooled table of the
+// rows [drow0 - bmax, drow0 + drows - bmax) from one read of the raw rows, then level after level the prior and
+// grid_track_kernel on those rows, then the selection, then the carry for the next chunk.
+hipError_t levels_chunk(GridJob& J, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
+{
+    const int bmax = J.lb[0], U = 2 * dev.ms - 1, KP = (dev.Na + 1) / 2;
+    const bool df = M.WS != nullptr;
+    int nw = 0;
+    for (int l = 0; l < J.L; l++) nw += J.lb[l] > 0 ? 1 : 0;
+    if (J.want_df && !df) { J.refused = "track: a dark-field map (df) needs the dark-field model"; return hipErrorInvalidValue; }
+    if (grid_basins_lds(dev.ms) > 64 * 1024) { J.refused = "track: the search box does not fit the kernel's ring of cost rows"; return hipErrorInvalidValue; }
+    const size_t n = (size_t)A.N0 * A.N1;
+    if (J.host && !J.block) {
+        if (hipMalloc(&J.block, levels_bytes(J.L, n)) != hipSuccess) { J.block = nullptr; return hipErrorOutOfMemory; }
+        levels_carve(J, J.block, n);
+    }
+    WidenGeom g;
+    g.b = bmax; g.U2 = U * U;
+    g.N0d = A.step0 * (A.N0 - 1) + 1; g.N1d = A.step1 * (A.N1 - 1) + 1;
+    g.drow0 = R.drow0; g.drows = R.drows; g.crows = R.drow0 == 0 ? 0 : 2 * bmax;
+    g.strip_w = R.strip_w; g.tw = R.tw; g.N1p = R.N1d; g.N1q = (g.N1d + 31) / 32 * 32;
+    widen_rows(bmax, g.N0d, g.drow0, g.drows, g.p0, g.p1);
+    const bool last = R.drow0 + R.drows >= g.N0d;
+    if (R.drow0 != J.next_drow0 || (!last && R.drows < 2 * bmax)) { J.refused = "levels: the row chunks do not follow each other"; return hipErrorInvalidValue; }
+    const size_t plane = (size_t)M.H * M.W, nmap = (2 + (df ? 4 * (size_t)KP : 0)) * plane;
+    if (!J.ws) {
+        J.pool_rows = std::min(g.N0d, g.drows + bmax);
+        if ((size_t)J.pool_rows * g.N1q >= ((size_t)1 << 32)) { J.refused = "levels: a plane of the pooled table passes the 32-bit stride of the lookups"; return hipErrorInvalidValue; }
+        const size_t pool_len = (size_t)g.U2 * J.pool_rows * g.N1q, carry_len = (last || bmax == 0) ? 0 : widen_table_len(g, 2 * bmax);
+        hipError_t e = hipMallocAsync(&J.ws, ((size_t)nw * (pool_len + nmap) + carry_len + 2 * n) * sizeof(double), s);
+        if (e != hipSuccess) { J.ws = nullptr; return hipErrorOutOfMemory; }
+        J.ws_stream = s;
+        double* q = (double*)J.ws;
+        for (int w = 0; w < nw; w++) { J.pools[w] = q; q += pool_len; }
+        J.carry = q; q += carry_len;
+        for (int w = 0; w < nw; w++) { J.lmaps[w] = q; q += nmap; }
+        J.prior = q;
+        for (int w = 0; w < nw; w++)                                   // (the widened levels come first in the list)
+            if ((e = widen_maps(J.lb[w], dev, M, A, g.N0d, g.N1d, J.lmaps[w], s)) != hipSuccess) return e;
+    }
+    if (g.p1 - g.p0 > J.pool_rows) { J.refused = "levels: a row chunk larger than the first"; return hipErrorInvalidValue; }
+    if (g.p1 > g.p0 && nw == 1) widen_table(g, R.table, J.carry, J.pools[0], s);   // g.b is that level's half-width
+    else if (g.p1 > g.p0 && nw > 1 && !levels_table(g, J.lb, nw, R.table, J.carry, J.pools, s)) {
+        J.refused = "levels: no pooling kernel for this list of half-widths"; return hipErrorInvalidValue;
+    }
+    int row0, rows;
+    levels_out_rows(g.p0, g.p1, A.step0, A.N0, row0, rows);
+    const unsigned blocks = (unsigned)(((size_t)rows * A.N1 + 255) / 256);
+    for (int l = 0; l < J.L && rows > 0 && A.N1 > 0; l++) {
+        const size_t at = (size_t)l * n, pv = l > 0 ? at - n : 0;
+        hipLaunchKernelGGL(levels_prior_kernel, dim3(blocks), dim3(256), 0, s, l > 0 ? (const double*)J.lev.dx + pv : nullptr,
+                           l > 0 ? (const double*)J.lev.dy + pv : nullptr, l > 0 ? (const int*)J.lev.err + pv : nullptr,
+                           J.prior, J.prior + n, A.N1, row0, rows);
+        J.K.pi = J.prior; J.K.pj = J.prior + n;
+        J.K.f = J.lev.f + at; J.K.T = J.lev.T + at; J.K.dx = J.lev.dx + at; J.K.dy = J.lev.dy + at; J.K.cost = J.lev.cost + at;
+        J.K.df = J.lev.df ? J.lev.df + at : nullptr; J.K.cost0 = J.lev.cost0 + at;
+        J.K.si = J.lev.si + at; J.K.sj = J.lev.sj + at; J.K.err = J.lev.err + at; J.K.count = J.lev.count + at; J.K.found = J.lev.found + at;
+        hipError_t e = hipSuccess;
+        if (J.lb[l] > 0) {                                            // widen_chunk's Mw, Rw: the level's pooled maps and table
+            Maps Mw = M;
+            ReplayArgs Rw = R;
+            Mw.SamSq = J.lmaps[l]; Mw.RefSq = J.lmaps[l] + plane;
+            Mw.WS = df ? J.lmaps[l] + 2 * plane : nullptr;
+            Mw.MR = df ? J.lmaps[l] + (2 + 2 * (size_t)KP) * plane : nullptr;
+            Rw.table = J.pools[l]; Rw.slot_stride = (size_t)(g.p1 - g.p0) * g.N1q; Rw.drow0 = g.p0; Rw.N1d = g.N1q;
+            Rw.strip_w = 0; Rw.tw = 0; Rw.drows = g.p1 - g.p0;
+            Rw.bw_log2 = 4;
+            Rw.row0 = row0; Rw.rows = rows;
+            e = dispatch(J, dev, Mw, Rw, A, s);
+        } else {                                                      // the model's own window: the raw rows, of the carry and of the chunk
+            int c0, c1, t0, t1;
+            levels_plain_rows(g, c0, c1, t0, t1);
+            ReplayArgs Rc = R, Rt = R;
+            Rc.table = J.carry; Rc.drow0 = g.drow0 - g.crows; Rc.drows = g.crows;
+            if (R.strip_w == 0) Rc.slot_stride = (size_t)g.crows * g.N1p;
+            levels_out_rows(c0, c1, A.step0, A.N0, Rc.row0, Rc.rows);
+            levels_out_rows(t0, t1, A.step0, A.N0, Rt.row0, Rt.rows);
+            e = dispatch(J, dev, M, Rc, A, s);
+            if (e == hipSuccess) e = dispatch(J, dev, M, Rt, A, s);
+        }
+        if (e != hipSuccess) return e;
+    }
+    if (J.want_sel && rows > 0 && A.N1 > 0) {
+        LevelsSelectArgs a;
+        a.lev = J.lev; a.sel = J.sel; a.level = J.sel_level; a.halfwidth = J.sel_hw;
+        a.plane = n; a.L = J.L; a.N1 = A.N1; a.row0 = row0; a.rows = rows;
+        for (int l = 0; l < UMPA_LEVELS_MAX; l++) { a.b[l] = J.lb[l]; a.tol[l] = J.ltol[l]; }
+        hipLaunchKernelGGL(levels_select_kernel, dim3(blocks), dim3(256), 0, s, a);
+    }
+    if (!last && bmax > 0) {
+        const WidenCarryCopy cc = widen_carry_copy(g);
+        hipLaunchKernelGGL(widen_carry_kernel, dim3((unsigned)((cc.run + 255) / 256), (unsigned)cc.nruns), dim3(256), 0, s, R.table, J.carry, cc);
+    }
+    J.next_drow0 = R.drow0 + R.drows;
+    return hipGetLastError();
+}
+
 hipError_t consumer(void* user, const ModelDev& dev, const Maps& M0, const ReplayArgs& R0, const RegionArgs& A0, hipStream_t s)
 {
     GridJob& J = *(GridJob*)user;
@@ -194,6 +381,7 @@ hipError_t consumer(void* user, const ModelDev& dev, const Maps& M0, const Repla
     ReplayArgs R = R0;
     RegionArgs A = A0;
     const int kind = M.WS ? 1 : 0;
+    if (J.L > 0) return levels_chunk(J, dev, M0, R0, A0, s);
     if (J.mhost) {
         const size_t n = (size_t)A.N0 * A.N1;
         if (!J.mblock) {
@@ -249,20 +437,7 @@ hipError_t consumer(void* user, const ModelDev& dev, const Maps& M0, const Repla
         const hipError_t e = widen_chunk(J, dev, M0, R0, A, s, M, R);
         if (e != hipSuccess) return e;
     }
-    if (R.rows <= 0 || A.N1 <= 0) return hipSuccess;
-    const bool small = (size_t)M.H * M.W * 2 * sizeof(double) < ((size_t)1 << 32);   // a pair plane (tiled_match)
-#define UMPA_GRID_NA(n) case n: launch<1, n>(J, dev, M, R, A, s); break;
-    if (kind == 1 && small && dev.Na <= UMPA_KTEMPL) {
-        switch (dev.Na) {
-            UMPA_GRID_NA(1) UMPA_GRID_NA(2) UMPA_GRID_NA(3) UMPA_GRID_NA(4) UMPA_GRID_NA(5) UMPA_GRID_NA(6)
-            UMPA_GRID_NA(7) UMPA_GRID_NA(8) UMPA_GRID_NA(9) UMPA_GRID_NA(10) UMPA_GRID_NA(11) UMPA_GRID_NA(12)
-            UMPA_GRID_NA(13) UMPA_GRID_NA(14) UMPA_GRID_NA(15) UMPA_GRID_NA(16) UMPA_GRID_NA(17) UMPA_GRID_NA(18)
-            UMPA_GRID_NA(19) UMPA_GRID_NA(20) UMPA_GRID_NA(21) UMPA_GRID_NA(22) UMPA_GRID_NA(23) UMPA_GRID_NA(24)
-        }
-    } else if (kind == 1) launch<1, 0>(J, dev, M, R, A, s);
-    else launch<0, 0>(J, dev, M, R, A, s);
-#undef UMPA_GRID_NA
-    return hipGetLastError();
+    return dispatch(J, dev, M, R, A, s);
 }
 
 // umpa_hip_match_region down the tiled path with `J` as the model's table consumer; the consumer is cleared whatever happens
@@ -463,6 +638,87 @@ int track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step
 // `b` outside 0 .. UMPA_GRID_MAX_WIDEN
 int bad_widen(int b) { return fail(UMPA_HIP_E_ARG, "grid: widen: the half-width b must be 0 to %d, not %d", UMPA_GRID_MAX_WIDEN, b); }
 
+// the list of half-widths as the refusal shows it: "(4, 2, 3)"
+std::string levels_text(int L, const int* b)
+{
+    std::string t = "(";
+    for (int l = 0; l < L; l++) t += (l ? ", " : "") + std::to_string(b[l]);
+    return t + ")";
+}
+
+int levels_track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                 int L, const int* b, int mode, double lam, double radius, const double* tol,
+                 const LevelsPlanes& lev, const LevelsPlanes& sel, int* level, int* halfwidth, int flags, void* stream)
+{
+    if (!m || !b || !lev.f || !lev.T || !lev.dx || !lev.dy || !lev.cost || !lev.si || !lev.sj || !lev.err || !lev.cost0 || !lev.count || !lev.found)
+        return fail(UMPA_HIP_E_ARG, "grid: levels: null argument");
+    if (L < 1 || L > UMPA_GRID_MAX_LEVELS) return fail(UMPA_HIP_E_ARG, "grid: levels: 1 to %d levels, not %d", UMPA_GRID_MAX_LEVELS, L);
+    if (levels_check(L, b))
+        return fail(UMPA_HIP_E_ARG, "grid: levels: the half-widths must decrease, the widened ones from {1, 2, 4, 8} and at most three, "
+                                    "a 0 only at the end, not %s", levels_text(L, b).c_str());
+    for (int l = 0; tol && l < L; l++)
+        if (!(tol[l] >= 0.0)) return fail(UMPA_HIP_E_ARG, "grid: levels: tol[%d] must be >= 0 or +Inf", l);
+    const int given = (sel.f != nullptr) + (sel.T != nullptr) + (sel.dx != nullptr) + (sel.dy != nullptr) + (sel.cost != nullptr) + (sel.si != nullptr)
+        + (sel.sj != nullptr) + (sel.err != nullptr) + (sel.cost0 != nullptr) + (sel.count != nullptr) + (sel.found != nullptr) + (level != nullptr) + (halfwidth != nullptr);
+    if ((given != 0 && given != 13) || (given == 0 && sel.df))
+        return fail(UMPA_HIP_E_ARG, "grid: levels: the selected arrays must be all given or all NULL");
+    if (mode != UMPA_GRID_TRACK_NEAREST && mode != UMPA_GRID_TRACK_PENALTY)
+        return fail(UMPA_HIP_E_ARG, "grid: track: mode must be UMPA_GRID_TRACK_NEAREST (0) or UMPA_GRID_TRACK_PENALTY (1), not %d", mode);
+    if (mode == UMPA_GRID_TRACK_PENALTY && !(lam >= 0.0 && lam < __builtin_inf()))
+        return fail(UMPA_HIP_E_ARG, "grid: track: lam must be finite and not negative");
+    if (radius != radius) return fail(UMPA_HIP_E_ARG, "grid: track: radius must not be NaN");
+    if (flags & ~(UMPA_HIP_F_DEVICE_IO | UMPA_HIP_F_USE_STAGED))
+        return fail(UMPA_HIP_E_ARG, "grid: track takes UMPA_HIP_F_DEVICE_IO, UMPA_HIP_F_USE_STAGED and no other flag");
+    const int staged = flags & UMPA_HIP_F_USE_STAGED;
+    GridJob J;
+    J.track = true;
+    J.L = L;
+    for (int l = 0; l < L; l++) { J.lb[l] = b[l]; J.ltol[l] = tol ? tol[l] : __builtin_inf(); }
+    J.want_df = lev.df != nullptr;
+    J.want_sel = given != 0;
+    J.K.mode = mode;
+    J.K.lam = mode == UMPA_GRID_TRACK_PENALTY ? lam : 0.0;
+    J.K.limited = radius < 0.0 ? 0 : 1;
+    J.K.r2 = radius < 0.0 ? 0.0 : radius * radius;
+    // value and status placeholders for the match entry point, as in umpa_grid_cost_volume
+    double* const no_values = lev.cost;
+    int* const no_err = (int*)lev.cost;
+    if (flags & UMPA_HIP_F_DEVICE_IO) {
+        J.lev = lev; J.sel = sel; J.sel_level = level; J.sel_hw = halfwidth;
+        if (!J.want_df) J.sel.df = nullptr;
+        return run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                   UMPA_HIP_F_DEVICE_IO | staged, stream);
+    }
+    // host arrays: one device block for the duration of the call, allocated by the consumer on the model's device, filled on
+    // that device's null stream and downloaded once when every chunk is enqueued (a level's rows are finished a chunk late)
+    J.host = true;
+    int rc = run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                 UMPA_HIP_F_DEVICE_IO | staged, nullptr);
+    if (!J.block) return rc;                                          // refused before the consumer ran: nothing was enqueued
+    hipError_t e = hipSuccess;
+    if (rc >= 0) {
+        const size_t n = (size_t)N0 * N1, ln = (size_t)L * n;
+        const struct { void* host; const void* dev; size_t bytes; } copies[26] = {
+            {lev.f, J.lev.f, ln * sizeof(double)}, {lev.T, J.lev.T, ln * sizeof(double)}, {lev.dx, J.lev.dx, ln * sizeof(double)},
+            {lev.dy, J.lev.dy, ln * sizeof(double)}, {lev.cost, J.lev.cost, ln * sizeof(double)}, {lev.df, J.lev.df, ln * sizeof(double)},
+            {lev.cost0, J.lev.cost0, ln * sizeof(double)},
+            {lev.si, J.lev.si, ln * sizeof(int)}, {lev.sj, J.lev.sj, ln * sizeof(int)}, {lev.err, J.lev.err, ln * sizeof(int)},
+            {lev.count, J.lev.count, ln * sizeof(int)}, {lev.found, J.lev.found, ln * sizeof(int)},
+            {sel.f, J.sel.f, n * sizeof(double)}, {sel.T, J.sel.T, n * sizeof(double)}, {sel.dx, J.sel.dx, n * sizeof(double)},
+            {sel.dy, J.sel.dy, n * sizeof(double)}, {sel.cost, J.sel.cost, n * sizeof(double)}, {sel.df, J.sel.df, n * sizeof(double)},
+            {sel.cost0, J.sel.cost0, n * sizeof(double)},
+            {sel.si, J.sel.si, n * sizeof(int)}, {sel.sj, J.sel.sj, n * sizeof(int)}, {sel.err, J.sel.err, n * sizeof(int)},
+            {sel.count, J.sel.count, n * sizeof(int)}, {sel.found, J.sel.found, n * sizeof(int)},
+            {level, J.sel_level, n * sizeof(int)}, {halfwidth, J.sel_hw, n * sizeof(int)}};
+        for (int q = 0; q < 26 && e == hipSuccess; q++)
+            if (copies[q].host && copies[q].dev) e = hipMemcpy(copies[q].host, copies[q].dev, copies[q].bytes, hipMemcpyDeviceToHost);
+    }
+    if (rc < 0 || e != hipSuccess) (void)hipDeviceSynchronize();      // nothing of this call may still use the block freed here
+    (void)hipFree(J.block);
+    if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the level maps: %s", hipGetErrorString(e));
+    return rc;
+}
+
 } // namespace
 
 UMPA_GRID_API const char* umpa_grid_last_error(void) { return g_err.c_str(); }
@@ -537,4 +793,18 @@ UMPA_GRID_API int umpa_grid_wide_track(umpa_hip_model* m, int start0, int step0,
     if (b < 0 || b > UMPA_GRID_MAX_WIDEN) return bad_widen(b);
     return track(m, start0, step0, N0, start1, step1, N1, b, prior_i, prior_j, mode, lam, radius,
                  f, T, dx, dy, cost, df, si, sj, err, cost0, count, found, flags, stream);
+}
+
+// Scale-space search: every level of half-widths b[0] > ... > b[L-1] from one table pass, and the selection per pixel.
+UMPA_GRID_API int umpa_grid_levels_track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                         int L, const int* b, int mode, double lam, double radius, const double* tol,
+                                         double* f, double* T, double* dx, double* dy, double* cost, double* df,
+                                         int* si, int* sj, int* err, double* cost0, int* count, int* found,
+                                         double* sel_f, double* sel_T, double* sel_dx, double* sel_dy, double* sel_cost, double* sel_df,
+                                         int* sel_si, int* sel_sj, int* sel_err, double* sel_cost0, int* sel_count, int* sel_found,
+                                         int* level, int* halfwidth, int flags, void* stream)
+{
+    const LevelsPlanes lev = {f, T, dx, dy, cost, df, cost0, si, sj, err, count, found};
+    const LevelsPlanes sel = {sel_f, sel_T, sel_dx, sel_dy, sel_cost, sel_df, sel_cost0, sel_si, sel_sj, sel_err, sel_count, sel_found};
+    return levels_track(m, start0, step0, N0, start1, step1, N1, L, b, mode, lam, radius, tol, lev, sel, level, halfwidth, flags, stream);
 }
