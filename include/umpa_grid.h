@@ -16,6 +16,8 @@
  *                           pixel: the same search under a window b pixels wider, on the same model ("window widening");
  *   umpa_grid_levels_track  umpa_grid_wide_track at up to four half-widths from one pass over the table, each level the prior
  *                           of the next, and per pixel the narrowest level that agrees with the wider ones ("scale space").
+ *   umpa_grid_sequence      a per-pixel cost state over all shifts carried from projection to projection: each call adds its
+ *                           costs to the cheapest compatible predecessor (forward dynamic programming, "sequence search").
  *
  * All work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
  * one shape at position (0, 0), steps and search ranges within that path's limits.  Anything else fails with
@@ -241,6 +243,56 @@ int umpa_grid_levels_track(umpa_hip_model *m, int start0, int step0, int N0, int
                            double *sel_f, double *sel_T, double *sel_dx, double *sel_dy, double *sel_cost, double *sel_df,
                            int *sel_si, int *sel_sj, int *sel_err, double *sel_cost0, int *sel_count, int *sel_found,
                            int *level, int *halfwidth, int flags, void *stream);
+
+/* Sequence search: one forward step of a dynamic programme over a series of projections.
+ *
+ * U = 2 max_shift - 1.  Shifts s = (si, sj) run in the grid search's scan order, rows (si) first, then columns (sj).  C[s] is
+ * the cost of umpa_grid_cost_volume at the pixel.  Everything is fp64 and nothing is contracted into a fused multiply-add.
+ * Every comparison is a plain `<` of doubles; every minimum starts at +Inf and takes a candidate iff it is `<` the best so
+ * far, the candidates in scan order (the first strict minimum): NaN and +Inf never win, -Inf is a number like any other.
+ *   State.   prev and next: [U * U][N0][N1] doubles in the slot order of the cost volume,
+ *            state[(si + max_shift - 1) * U + (sj + max_shift - 1)][xi][xj].  prev may be NULL: a series starts.  next may be
+ *            NULL (the state is not kept).  prev and next must not overlap.
+ *   Transition.  lam is finite and >= 0, trunc is >= 0 or +Inf.
+ *            1. m0 = min_{s'} prev[s'].  If prev is NULL or !(m0 < +Inf) -- the pixel never matched -- M[s] = 0 for all s.
+ *               Otherwise
+ *            2. R[si'][sj] = min_{sj'} (prev[si'][sj'] + lam * (double)((sj - sj') * (sj - sj'))), sj' ascending: the square
+ *               in ints, one conversion, one product and one sum, each rounded;
+ *            3. Q[si][sj]  = min_{si'} (R[si'][sj] + lam * (double)((si - si') * (si - si'))), si' ascending;
+ *            4. cap = m0 + trunc;  Q'[s] = (cap < Q[s]) ? cap : Q[s];
+ *            5. M[s] = Q'[s] - m0.
+ *            This two-stage form IS the definition of the quadratic penalty here, not an approximation of the joint minimum
+ *            over s' (with exact arithmetic the two agree; in doubles the order of the two sums is this one).  The truncation
+ *            lets a pixel jump to any shift at the fixed price trunc.  Taking m0 off keeps the numbers on the scale of one
+ *            projection's costs however long the series is.
+ *   Update.  A[s] = C[s] + M[s], one sum; next[s] = A[s] where next is not NULL.  A[s] is NaN where C[s] is NaN.
+ *   Choice.  s* is the first strict minimum of A.
+ *   Outputs, planes [N0][N1].  For s*: f, T, dx, dy, df (doubles) and si, sj, err (ints), exactly what umpa_grid_track writes
+ *            for a chosen basin, evaluated on the DATA costs C: quadrant rule, 4x4 neighbourhood, the model's sub-pixel mode,
+ *            T (df) of the integer shift, err = 1, or err = 0 with the integer shift and its cost where the 4x4 leaves the
+ *            box.  cost = C[s*].  total = A[s*].  cost0: the first strict minimum of C (0 where no C[s] < +Inf).  moved (int):
+ *            1 iff s* differs from the first strict minimum of C.
+ *            No A[s] < +Inf: err = -1, f = T = dx = dy = cost = total (= df) = 0, si = sj = 0, moved = 0; next is written all
+ *            the same.
+ *   Consequences.  With lam = 0 (and a prev without -Inf) Q = m0 everywhere, so M = 0 and A = C + 0.0, which compares like C:
+ *            f, T, dx, dy, df, err are those of umpa_grid_match_region, and cost = total = cost0, moved = 0.  The same with
+ *            prev = NULL.  With trunc = 0, M = 0 at every pixel whose m0 is finite.
+ *            A pixel's result depends on that pixel's state and costs alone: the maps and next are the same bit for bit from
+ *            run to run, for host and device arrays and under any row chunking.  No atomics.
+ *
+ * The model and the region as for umpa_grid_track, with max_shift from 2 to UMPA_GRID_SEQUENCE_MAX_SHIFT (the range of
+ * umpa_smooth); any other max_shift is UMPA_HIP_E_UNSUPPORTED and the text names the value.  Host arrays, or device arrays
+ * with UMPA_HIP_F_DEVICE_IO (the call then only enqueues work on `stream`) -- prev, next and the maps alike;
+ * UMPA_HIP_F_USE_STAGED as for umpa_grid_cost_volume.  df may be NULL (dark-field model only: UMPA_HIP_E_* with a plain model).
+ * Checked in this order, before anything touches a device, each UMPA_HIP_E_ARG with a text that names the value: a NULL
+ * model; a NULL output plane (other than df and next); a lam that is NaN, infinite or negative; a trunc that is NaN or
+ * negative; a flag other than the two above. */
+#define UMPA_GRID_SEQUENCE_MAX_SHIFT 8
+int umpa_grid_sequence(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
+                       const double *prev, double lam, double trunc, double *next,
+                       double *f, double *T, double *dx, double *dy, double *cost, double *df,
+                       int *si, int *sj, int *err, double *total, double *cost0, int *moved,
+                       int flags, void *stream);
 
 const char *umpa_grid_last_error(void);
 

@@ -25,6 +25,9 @@ volume on ``libumpa_smooth.so`` and start the ordinary walk from it.
 on the same model; ``umpa_amd.widen`` has that window, the region of a widened result and ``coarse_to_fine``.
 ``scale_space`` (``umpa_amd.levels``) runs every widening level of that chain from one pass over the shift table and picks,
 per pixel, the narrowest level that agrees with every wider one; ``select_levels`` states the rule in numpy.
+``model.sequence()`` carries a per-pixel cost state through a series of projections (forward dynamic programming over the
+shift table), so that one bad projection does not lock a wrong basin in; ``Sequence`` (``umpa_amd.sequence``) runs a step
+series on it with the state on the device, ``restate`` states the rule in numpy.
 """
 from . import model
 from . import align
@@ -45,6 +48,8 @@ from .track import Tracker, prior_from
 from . import widen
 from . import levels
 from .levels import scale_space, select_levels
+from . import sequence
+from .sequence import Sequence, restate
 
 __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAModelDF", "UMPAModelDFKernel",
            "UnwarpMap", "integrate", "vcycle", "phase_from_match", "Integration",
@@ -54,4 +59,5 @@ __all__ = ["model", "align", "match", "match_unbiased", "UMPAModelNoDF", "UMPAMo
            "basins",
            "track", "Tracker", "prior_from",
            "widen",
-           "levels", "scale_space", "select_levels"]
+           "levels", "scale_space", "select_levels",
+           "sequence", "Sequence", "restate"]

@@ -1,7 +1,8 @@
 // umpa_grid.hip -- libumpa_grid.so: exhaustive grid search and the cost volume (include/umpa_grid.h).  gfx950 only.
 //
 // A second library, built from the headers of libumpa_hip.so by the same build: it holds the kernel families of
-// umpa_grid_kernels.h, umpa_basins_kernels.h, umpa_track_kernels.h, umpa_widen_kernels.h and umpa_levels_kernels.h and no other feature code.  A call sets itself as the model's table
+// umpa_grid_kernels.h, umpa_basins_kernels.h, umpa_track_kernels.h, umpa_widen_kernels.h, umpa_levels_kernels.h and
+// umpa_sequence_kernels.h and no other feature code.  A call sets itself as the model's table
 // consumer (umpa_hipx.h), runs umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include "umpa_track_kernels.h"
 #include "umpa_widen_kernels.h"
 #include "umpa_levels_kernels.h"
+#include "umpa_sequence_kernels.h"
 
 using namespace umpa;
 
@@ -73,6 +75,16 @@ struct GridJob {
     int* sel_level = nullptr;
     int* sel_hw = nullptr;
     bool want_sel = false;
+    // umpa_grid_sequence: grid_sequence_kernel; host arrays: `block` holds the previous state (uploaded by the consumer before
+    // the first chunk's kernel), the next state and the twelve maps
+    bool sequence = false;
+    SequenceArgs Q = {};
+    const double* host_prev = nullptr;
+    bool want_next = false;
+    size_t state_len = 0;             // doubles per state: U * U * N0 * N1 (known at the first chunk)
+    // a refusal of the consumer with a code of its own (otherwise the match entry point's) and a text that names a value
+    int refused_code = 0;
+    std::string refused_text;
 };
 
 // the block of umpa_grid_wide_match_region's host path: values, dbg_d, dbg_a, cover (doubles), then err, dbg_n (ints)
@@ -115,11 +127,33 @@ void track_carve(TrackArgs& K, void* block, size_t plane, bool df)
 }
 size_t track_bytes(size_t plane) { return 9 * plane * sizeof(double) + 5 * plane * sizeof(int); }
 
+// umpa_grid_sequence's block: the two states (U2 planes each; absent ones take no room), eight planes of doubles (the six
+// double maps in the order of the arguments, total, cost0), then four of ints
+void sequence_carve(SequenceArgs& Q, void* block, size_t plane, int U2, bool prev, bool next, bool df)
+{
+    double* d = (double*)block;
+    Q.prev = prev ? d : nullptr; d += prev ? U2 * plane : 0;
+    Q.next = next ? d : nullptr; d += next ? U2 * plane : 0;
+    Q.f = d; Q.T = d + plane; Q.dx = d + 2 * plane; Q.dy = d + 3 * plane; Q.cost = d + 4 * plane;
+    Q.df = df ? d + 5 * plane : nullptr;
+    Q.total = d + 6 * plane; Q.cost0 = d + 7 * plane;
+    int* q = (int*)(d + 8 * plane);
+    Q.si = q; Q.sj = q + plane; Q.err = q + 2 * plane; Q.moved = q + 3 * plane;
+}
+size_t sequence_bytes(size_t plane, int U2, bool prev, bool next)
+{
+    return ((size_t)U2 * ((prev ? 1 : 0) + (next ? 1 : 0)) + 8) * plane * sizeof(double) + 4 * plane * sizeof(int);
+}
+
 // the frame count as a template constant exactly where replay_walk's dispatch has it (tiled_match)
 template <int KIND, int NA>
 void launch(const GridJob& J, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
 {
-    if (J.track) {
+    if (J.sequence) {                                                 // (a wave takes 64 or 32 pixels: SequenceArgs::half)
+        const int bw = 1 << R.bw_log2, bh = (64 >> J.Q.half) >> R.bw_log2;
+        hipLaunchKernelGGL((grid_sequence_kernel<KIND, NA>), dim3((A.N1 + bw - 1) / bw, (R.rows + bh - 1) / bh), dim3(64),
+                           sequence_lds(dev.ms, J.Q.prev != nullptr), s, dev, M, R, A, J.Q);
+    } else if (J.track) {
         const int bw = 1 << R.bw_log2, bh = 64 >> R.bw_log2;
         hipLaunchKernelGGL((grid_track_kernel<KIND, NA>), dim3((A.N1 + bw - 1) / bw, (R.rows + bh - 1) / bh), dim3(64),
                            grid_basins_lds(dev.ms), s, dev, M, R, A, J.K);
@@ -433,6 +467,28 @@ hipError_t consumer(void* user, const ModelDev& dev, const Maps& M0, const Repla
             if (e != hipSuccess) return e;
         }
     }
+    if (J.sequence) {
+        if (dev.ms < 2 || dev.ms > UMPA_GRID_SEQUENCE_MAX_SHIFT) {
+            char text[128];
+            snprintf(text, sizeof(text), "sequence: max_shift must be 2 to %d, not %d", UMPA_GRID_SEQUENCE_MAX_SHIFT, dev.ms);
+            J.refused_text = text; J.refused = J.refused_text.c_str(); J.refused_code = UMPA_HIP_E_UNSUPPORTED;
+            return hipErrorInvalidValue;
+        }
+        if (J.want_df && kind != 1) { J.refused = "sequence: a dark-field map (df) needs the dark-field model"; return hipErrorInvalidValue; }
+        const int U = 2 * dev.ms - 1;
+        const size_t plane = (size_t)A.N0 * A.N1;
+        J.Q.plane = plane;
+        J.Q.half = sequence_half(dev.ms);
+        J.state_len = (size_t)U * U * plane;
+        if (J.host && !J.block) {
+            if (hipMalloc(&J.block, sequence_bytes(plane, U * U, J.host_prev != nullptr, J.want_next)) != hipSuccess) { J.block = nullptr; return hipErrorOutOfMemory; }
+            sequence_carve(J.Q, J.block, plane, U * U, J.host_prev != nullptr, J.want_next, J.want_df);
+            if (J.host_prev) {
+                const hipError_t e = hipMemcpy((void*)J.Q.prev, J.host_prev, J.state_len * sizeof(double), hipMemcpyHostToDevice);
+                if (e != hipSuccess) return e;
+            }
+        }
+    }
     if (J.b > 0) {
         const hipError_t e = widen_chunk(J, dev, M0, R0, A, s, M, R);
         if (e != hipSuccess) return e;
@@ -450,7 +506,7 @@ int run(umpa_hip_model* m, GridJob& J, int start0, int step0, int N0, int start1
                                          dbg_d, dbg_a, dbg_n, flags | UMPA_HIP_F_FORCE_TILED, stream);
     (void)umpa_hipx_set_table_consumer(m, nullptr, nullptr);
     if (J.ws) { (void)hipFreeAsync(J.ws, J.ws_stream); J.ws = nullptr; }   // (widening) behind the call's last kernel on its stream
-    if (rc < 0) return fail(rc, "grid: %s", J.refused ? J.refused : umpa_hip_last_error());
+    if (rc < 0) return fail(J.refused && J.refused_code ? J.refused_code : rc, "grid: %s", J.refused ? J.refused : umpa_hip_last_error());
     return rc;
 }
 
@@ -635,6 +691,61 @@ int track(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step
     return rc;
 }
 
+int sequence(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+             const double* prev, double lam, double trunc, double* next,
+             double* f, double* T, double* dx, double* dy, double* cost, double* df,
+             int* si, int* sj, int* err, double* total, double* cost0, int* moved, int flags, void* stream)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "grid: sequence: null model");
+    if (!f || !T || !dx || !dy || !cost || !si || !sj || !err || !total || !cost0 || !moved)
+        return fail(UMPA_HIP_E_ARG, "grid: sequence: null output plane (only df and next may be NULL)");
+    if (!(lam >= 0.0 && lam < __builtin_inf())) return fail(UMPA_HIP_E_ARG, "grid: sequence: lam must be finite and not negative, not %g", lam);
+    if (!(trunc >= 0.0)) return fail(UMPA_HIP_E_ARG, "grid: sequence: trunc must be >= 0 or +Inf, not %g", trunc);
+    if (flags & ~(UMPA_HIP_F_DEVICE_IO | UMPA_HIP_F_USE_STAGED))
+        return fail(UMPA_HIP_E_ARG, "grid: sequence takes UMPA_HIP_F_DEVICE_IO, UMPA_HIP_F_USE_STAGED and no other flag, not 0x%x", (unsigned)flags);
+    const int staged = flags & UMPA_HIP_F_USE_STAGED;
+    GridJob J;
+    J.sequence = true;
+    J.want_df = df != nullptr;
+    J.want_next = next != nullptr;
+    J.Q.lam = lam; J.Q.trunc = trunc;
+    // value and status placeholders for the match entry point, as in umpa_grid_cost_volume: with device I/O nothing reads,
+    // seeds or clears them
+    double* const no_values = cost;
+    int* const no_err = (int*)cost;
+    if (flags & UMPA_HIP_F_DEVICE_IO) {
+        J.Q.prev = prev; J.Q.next = next;
+        J.Q.f = f; J.Q.T = T; J.Q.dx = dx; J.Q.dy = dy; J.Q.cost = cost; J.Q.df = df; J.Q.total = total; J.Q.cost0 = cost0;
+        J.Q.si = si; J.Q.sj = sj; J.Q.err = err; J.Q.moved = moved;
+        return run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                   UMPA_HIP_F_DEVICE_IO | staged, stream);
+    }
+    // host arrays: one device block for the duration of the call, allocated and given the previous state by the consumer on
+    // the model's device (which stays this thread's current device), filled on that device's null stream
+    J.host = true;
+    J.host_prev = prev;
+    int rc = run(m, J, start0, step0, N0, start1, step1, N1, no_values, 7, no_err, nullptr, 0.0, nullptr, nullptr, nullptr,
+                 UMPA_HIP_F_DEVICE_IO | staged, nullptr);
+    if (!J.block) return rc;                                          // refused before the consumer allocated: nothing was enqueued
+    hipError_t e = hipSuccess;
+    if (rc >= 0) {
+        const size_t plane = (size_t)N0 * N1;
+        const struct { void* host; const void* dev; size_t bytes; } copies[13] = {
+            {next, J.Q.next, J.state_len * sizeof(double)},
+            {f, J.Q.f, plane * sizeof(double)}, {T, J.Q.T, plane * sizeof(double)}, {dx, J.Q.dx, plane * sizeof(double)},
+            {dy, J.Q.dy, plane * sizeof(double)}, {cost, J.Q.cost, plane * sizeof(double)}, {df, J.Q.df, plane * sizeof(double)},
+            {total, J.Q.total, plane * sizeof(double)}, {cost0, J.Q.cost0, plane * sizeof(double)},
+            {si, J.Q.si, plane * sizeof(int)}, {sj, J.Q.sj, plane * sizeof(int)}, {err, J.Q.err, plane * sizeof(int)},
+            {moved, J.Q.moved, plane * sizeof(int)}};
+        for (int q = 0; q < 13 && e == hipSuccess; q++)
+            if (copies[q].host && copies[q].dev) e = hipMemcpy(copies[q].host, copies[q].dev, copies[q].bytes, hipMemcpyDeviceToHost);
+    }
+    if (rc < 0 || e != hipSuccess) (void)hipDeviceSynchronize();      // nothing of this call may still use the block freed here
+    (void)hipFree(J.block);
+    if (rc >= 0 && e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: download of the sequence maps and state: %s", hipGetErrorString(e));
+    return rc;
+}
+
 // `b` outside 0 .. UMPA_GRID_MAX_WIDEN
 int bad_widen(int b) { return fail(UMPA_HIP_E_ARG, "grid: widen: the half-width b must be 0 to %d, not %d", UMPA_GRID_MAX_WIDEN, b); }
 
@@ -752,6 +863,15 @@ UMPA_GRID_API int umpa_grid_track(umpa_hip_model* m, int start0, int step0, int 
 {
     return track(m, start0, step0, N0, start1, step1, N1, 0, prior_i, prior_j, mode, lam, radius,
                  f, T, dx, dy, cost, df, si, sj, err, cost0, count, found, flags, stream);
+}
+
+UMPA_GRID_API int umpa_grid_sequence(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                     const double* prev, double lam, double trunc, double* next,
+                                     double* f, double* T, double* dx, double* dy, double* cost, double* df,
+                                     int* si, int* sj, int* err, double* total, double* cost0, int* moved, int flags, void* stream)
+{
+    return sequence(m, start0, step0, N0, start1, step1, N1, prev, lam, trunc, next, f, T, dx, dy, cost, df, si, sj, err,
+                    total, cost0, moved, flags, stream);
 }
 
 // Window widening: the NULL check of the sibling, the range of `b`, then the sibling's checks in their order.

@@ -715,6 +715,96 @@ class UMPAModelBase:
             out['err'] = np.maximum(err, 0)
         return out
 
+    def _grid_sequence(self, state, lam, trunc, ROI, step, alloc):
+        """The one ``umpa_grid_sequence`` call.  ``state(U, N0, N1)`` gives the previous state (float64 ``[U, U, N0, N1]``, or
+        None: a series starts) and ``alloc(U, N0, N1)`` the output arrays once the model and the region have passed: a
+        dictionary of ``state`` (the next state, float64 ``[U, U, N0, N1]``), ``f``, ``T``, ``dx``, ``dy``, ``cost``, ``total``,
+        ``cost0`` (and ``df``: dark-field model) as float64 ``[N0, N1]`` and ``si``, ``sj``, ``err``, ``moved`` as int32 -- all host
+        arrays, or all HIP tensors that the library reads and fills on the current stream.  This call is given the staged
+        stack, so it spends the one-shot flag.  Returns ``(s0, s1, arrays)``."""
+        self._grid_check("sequence")
+        s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
+        U = 2 * self._max_shift - 1
+        prev = state(U, N0, N1)
+        out = alloc(U, N0, N1)
+        _, flags, stream = _lib.Side(prev, *out.values(), device=self._device,
+                                     mixed="sequence: the state and the outputs must be all host arrays or all HIP tensors").tail(self._staged_flag())
+        names = ('f', 'T', 'dx', 'dy', 'cost', 'df', 'si', 'sj', 'err', 'total', 'cost0', 'moved')
+        args = [self._handle, s0[0], s0[2], N0, s1[0], s1[2], N1, _lib.Side.ptr(prev), float(lam), float(trunc), _lib.Side.ptr(out.get('state'))]
+        args += [_lib.Side.ptr(out.get(n)) for n in names] + [flags, stream]
+        try:
+            _lib.grid().check(_lib.grid().sequence(*args), "grid sequence")
+        except _lib.NativeError as e:
+            raise RuntimeError("sequence: %s" % e) from None
+        return s0, s1, out
+
+    def _sequence(self, state=None, lam=None, trunc=None, ROI=None, step=None, out=None):
+        self._grid_check("sequence")
+        if not _lib.GRID_SEQUENCE_MIN_MS <= self._max_shift <= _lib.GRID_SEQUENCE_MAX_MS:
+            raise RuntimeError("sequence: max_shift must be %d to %d, not %d" % (_lib.GRID_SEQUENCE_MIN_MS, _lib.GRID_SEQUENCE_MAX_MS, self._max_shift))
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+        if not (number(lam) and 0.0 <= float(lam) < np.inf):
+            raise ValueError("sequence: lam must be a finite number >= 0, not %r" % (lam,))
+        if trunc is not None and not (number(trunc) and float(trunc) >= 0.0):
+            raise ValueError("sequence: trunc must be None (no truncation) or a number >= 0, not %r" % (trunc,))
+        given = [a for a in (state, out) if a is not None]
+        on_device = [hasattr(a, "data_ptr") for a in given]
+        if any(on_device) and not all(on_device):
+            raise ValueError("sequence: state and out must be both numpy arrays or both HIP tensors")
+        dev = given[0].device if any(on_device) else None
+
+        def held(a, what, U, N0, N1):
+            """`a` as the library takes a state: float64 [U, U, N0, N1], contiguous, on the call's side"""
+            shape = tuple(a.shape) if dev is not None else np.shape(a)
+            if shape != (U, U, N0, N1):
+                raise ValueError("sequence: %s must be of shape %s, not %s" % (what, (U, U, N0, N1), shape))
+            if dev is not None:
+                import torch
+                if a.dtype != torch.float64 or not a.is_cuda or a.device.index != self._device or not a.is_contiguous():
+                    raise ValueError("sequence: a device %s must be a contiguous float64 HIP tensor on the model's device" % what)
+                return a
+            if np.asarray(a).dtype.kind not in "fiu":
+                raise ValueError("sequence: %s must be of a real number type, not %s" % (what, np.asarray(a).dtype))
+            return a
+
+        def prev(U, N0, N1):
+            if state is None:
+                return None
+            a = held(state, "state", U, N0, N1)
+            return a if dev is not None else np.ascontiguousarray(a, dtype=NPDOUBLE)   # (no copy of a float64 array)
+
+        dbl = ['f', 'T', 'dx', 'dy', 'cost', 'total', 'cost0'] + (['df'] if self._kind == KIND_DF else [])
+        ints = ('si', 'sj', 'err', 'moved')
+
+        def alloc(U, N0, N1):
+            if out is not None:
+                nxt = held(out, "out", U, N0, N1)
+                if dev is None and not (isinstance(out, np.ndarray) and out.dtype == NPDOUBLE and out.flags.c_contiguous):
+                    raise ValueError("sequence: a host out must be a C-contiguous float64 numpy array")
+                if state is not None and _lib.Side.ptr(nxt) == _lib.Side.ptr(state):
+                    raise ValueError("sequence: out must not be the state itself (the call reads the one while it writes the other)")
+            if dev is not None:
+                import torch
+                res = {'state': out if out is not None else torch.empty((U, U, N0, N1), dtype=torch.float64, device=dev)}
+                res.update({n: torch.empty((N0, N1), dtype=torch.float64, device=dev) for n in dbl})
+                res.update({n: torch.empty((N0, N1), dtype=torch.int32, device=dev) for n in ints})
+                return res
+            res = {'state': out if out is not None else np.empty((U, U, N0, N1), dtype=NPDOUBLE)}
+            res.update({n: _lib.pinned_empty((N0, N1), NPDOUBLE) for n in dbl})   # page-locked, as the result maps of match()
+            res.update({n: _lib.pinned_empty((N0, N1), np.int32) for n in ints})
+            return res
+
+        _, _, res = self._grid_sequence(prev, lam, np.inf if trunc is None else trunc, ROI, step, alloc)
+        si, sj, err = res.pop('si'), res.pop('sj'), res.pop('err')
+        if dev is not None:
+            import torch
+            res['shift'] = torch.stack([si, sj], dim=0)
+            res['err'] = torch.clamp(err, min=0)
+        else:
+            res['shift'] = np.stack([si, sj], axis=0)
+            res['err'] = np.maximum(err, 0)
+        return res
+
     _force = 0
     _use_staged = False
     _sam_staged = False        # the sample stack came from stage_sample: self._sam is not the stack the library matches
@@ -757,7 +847,7 @@ class UMPAModelBase:
         float32 / uint16 (page-locked arrays -- ``_lib.pinned_empty`` -- make this return at once); ``dark`` / ``flat``:
         device float64 stacks (lists of 2-D HIP tensors) for the fused ``(raw - dark) / flat`` of ``umpa_multi.py:144``.
         The staged stack becomes the sample stack of the next call that reads the sample stack -- ``match()``,
-        ``cost_volume()``, ``basins()``, ``track()``, ``match_smooth`` -- and stays it.  The last stack wins: another ``stage_sample`` or
+        ``cost_volume()``, ``basins()``, ``track()``, ``sequence()``, ``match_smooth`` -- and stays it.  The last stack wins: another ``stage_sample`` or
         ``update_frames(sam_list=...)`` before that call replaces it.  The model keeps no host copy of a staged stack:
         ``uncertainty()`` then needs it as ``sam=``."""
         if not self._lib.is_hip or hasattr(self._sam[0], "data_ptr"):
@@ -995,6 +1085,28 @@ class _UMPAModelPlain(UMPAModelBase):
         ``ROI`` / ``step``, the staged stack and the admitted models as for ``basins()``.  ``widen``: as for ``match()``; the
         priors then have the shape of the result (the kept region) or are scalars."""
         return self._track(prior_dx, prior_dy, lam=lam, radius=radius, ROI=ROI, step=step, widen=widen)
+
+    def sequence(self, state=None, lam=None, trunc=None, ROI=None, step=None, out=None):
+        """Sequence search (extension; ``include/umpa_grid.h``: ``umpa_grid_sequence`` has the definition): one forward step of
+        a dynamic programme over a series of projections.  ``state`` holds, per pixel, an accumulated cost for every shift of
+        the search box -- float64 ``[U, U, N0, N1]``, ``U = 2 max_shift - 1``, laid out like ``cost_volume()`` -- or is ``None``
+        where a series starts.  This projection's cost of a shift is added to the cheapest predecessor, where moving from
+        shift ``s'`` to ``s`` costs ``lam * |s - s'|^2`` (rows, then columns: the two-stage form of the header) and never more
+        than ``trunc`` above the best predecessor (``None``: no truncation); the minimum of the state is taken off, so that
+        the numbers stay on the scale of one projection's costs.  The shift with the lowest sum is finished like
+        ``match(search='grid')`` finishes its minimum, on this projection's costs.
+
+        Returns the dictionary of ``match()`` -- ``dx``, ``dy``, ``f``, ``T`` (``df``), ``err`` -- plus ``cost`` (this projection's
+        cost of the chosen integer shift), ``total`` (its accumulated cost), ``cost0`` (the lowest cost of this projection
+        alone), ``shift`` int32 ``[2, N0, N1]`` (row shift first), ``moved`` (int32: 1 where the series overruled this
+        projection's own minimum) and ``state``, the state to hand to the next projection's call.  ``lam=0`` and
+        ``state=None`` both give the maps of ``match(search='grid')``.
+
+        ``state`` (and ``out``, an array the next state is written into instead of a new one) are numpy arrays, or float64
+        HIP tensors on the model's device -- then everything comes back as HIP tensors.  ``ROI`` / ``step``, the staged stack
+        and the admitted models as for ``track()``; ``max_shift`` 2 to 8.  ``umpa_amd.Sequence`` keeps the state of a step
+        series on the device."""
+        return self._sequence(state=state, lam=lam, trunc=trunc, ROI=ROI, step=step, out=out)
 
     def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
         """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
