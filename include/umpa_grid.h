@@ -21,7 +21,8 @@
  *
  * All work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
  * one shape at position (0, 0), steps and search ranges within that path's limits.  Anything else fails with
- * UMPA_HIP_E_UNSUPPORTED before a kernel is launched.  Models are created, configured and destroyed through
+ * UMPA_HIP_E_UNSUPPORTED before a kernel is launched.  A model WITH masks is admitted once umpa_grid_set_masked has
+ * switched it on (below; off by default).  Models are created, configured and destroyed through
  * include/umpa_hip.h; link both libraries.  Error text: umpa_hip_last_error() for codes that umpa_hip_match_region
  * produced, umpa_grid_last_error() for this library's own.
  */
@@ -33,6 +34,29 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+/* Masked models: the per-model switch, off by default.  A NULL model is UMPA_HIP_E_ARG; on a model without masks the call
+ * changes nothing; the state lives with the model and dies with it.
+ *
+ * With the switch off, every function below refuses a model with masks as before (UMPA_HIP_E_UNSUPPORTED, the same text).
+ * With it on, umpa_grid_match_region, _cost_volume, _basins, _track, _sequence and the umpa_grid_wide_ four with b = 0 run on
+ * the MASKED tiled path's table, which holds, for every integer shift of the search box at every dense pixel, the finished
+ * cost, transmission and dark-field of the masked model (the numbers its walk reads: DESIGN.md sections 4.4 and 4.16).  Every
+ * rule stated below then holds word for word with C[s] that cost: argument checks, their order and texts, flags, chunked
+ * downloads and the rows callback are unchanged, and so are the equivalences (rank 0 of the basins is the grid minimum,
+ * track with lam = 0 and sequence with lam = 0 or without a state are the grid search).
+ * Coverage.  umpa_grid_match_region takes `covermap` / `cover_threshold` and skips the pixels below the threshold, as
+ * umpa_hip_match_region does.  The other functions have no such argument: on a masked model they compute EVERY pixel of the
+ * region, and the caller drops the pixels it does not trust.  A window without any pair weight has a weight sum of 0, all
+ * its costs are NaN, and the NaN rules below give the "no finite cost" result; a window that keeps some weight has costs,
+ * however few pixels carry them.
+ * What the masked tiled path does not take is UMPA_HIP_E_UNSUPPORTED with a text that names the reason: a window size without
+ * a masked table kernel, exact-fit windows (frames x window pixels <= 9), a dark-field pair plane past 4 GiB, a step product
+ * past the masked limit (16 dense pixels per requested one, 5 for the dark-field model, at up to 81 shifts; fewer beyond),
+ * frames at different positions or of different shapes.
+ * Window widening (b > 0) and umpa_grid_levels_track on such a model are UMPA_HIP_E_UNSUPPORTED: a finished cost is not linear
+ * in the windowed sums, so a box average of costs is not the cost under a wider window. */
+int umpa_grid_set_masked(umpa_hip_model *m, int on);
 
 /* The arguments, flags (UMPA_HIP_F_DEVICE_IO, _PLANAR, _REUSE_REF_MAPS, _USE_STAGED, _ASYNC), chunked downloads and the
  * rows callback of umpa_hip_match_region.  `uv` must be NULL (start shifts mean nothing to an exhaustive search:
@@ -101,7 +125,8 @@ int umpa_grid_cost_volume(umpa_hip_model *m, int start0, int step0, int N0, int 
  * (column), err; and count[N0][N1].  Host arrays, or device arrays with UMPA_HIP_F_DEVICE_IO (the call then only enqueues
  * work on `stream`); UMPA_HIP_F_USE_STAGED as for umpa_grid_cost_volume; any other flag is UMPA_HIP_E_ARG.  Checked in this
  * order, before anything touches a device: a NULL model or array (other than df), K outside 1 .. 8, the flags -- each
- * UMPA_HIP_E_ARG.  No coverage map: the models this library admits are covered everywhere.
+ * UMPA_HIP_E_ARG.  No coverage map: every pixel of the region is computed; on a masked model (umpa_grid_set_masked) a window
+ * without any pair weight has NaN costs and comes out as a pixel without a finite cost.
  * One pass over the table, no atomics: the output is the same bit for bit from run to run, for host and device arrays and
  * under any row chunking. */
 int umpa_grid_basins(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1, int K,

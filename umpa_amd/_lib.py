@@ -178,6 +178,8 @@ _GRID_ABI["levels_track"] = (_int, [_vp] + [_int] * 6 + [_int, _vp, _int, _dbl, 
 # umpa_grid_sequence: the model and the region, prev, lam, trunc, next, the nine maps of track, total, cost0 and moved
 GRID_SEQUENCE_MIN_MS, GRID_SEQUENCE_MAX_MS = 2, 8                # the search ranges umpa_grid_sequence admits
 _GRID_ABI["sequence"] = (_int, [_vp] + [_int] * 6 + [_vp, _dbl, _dbl, _vp] + [_vp] * 12 + [_int, _vp])
+# umpa_grid_set_masked: the model, on / off (the per-model switch that admits a masked model to the calls above)
+_GRID_ABI["set_masked"] = (_int, [_vp, _int])
 GRID_SYMBOLS = list(_GRID_ABI)
 
 # include/umpa_unwarp.h: detector distortion correction, stand-alone and fused into stage_sample of models of libumpa_hip.so

@@ -2,7 +2,8 @@
 //
 // A second library, built from the headers of libumpa_hip.so by the same build: it holds the kernel families of
 // umpa_grid_kernels.h, umpa_basins_kernels.h, umpa_track_kernels.h, umpa_widen_kernels.h, umpa_levels_kernels.h and
-// umpa_sequence_kernels.h and no other feature code.  A call sets itself as the model's table
+// umpa_sequence_kernels.h, their twins on a masked model's table of finished costs (umpa_masked_grid_kernels.h) and no other
+// feature code.  A call sets itself as the model's table
 // consumer (umpa_hipx.h), runs umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 #include "umpa_widen_kernels.h"
 #include "umpa_levels_kernels.h"
 #include "umpa_sequence_kernels.h"
+#include "umpa_masked_grid_kernels.h"
 
 using namespace umpa;
 
@@ -85,6 +87,9 @@ struct GridJob {
     // a refusal of the consumer with a code of its own (otherwise the match entry point's) and a text that names a value
     int refused_code = 0;
     std::string refused_text;
+    // an admitted masked model (umpa_grid_set_masked): the planes per shift of its table of finished costs, 2 or 3
+    // (umpa_hipx_masked_table); 0: the plain path's table.  The kernels are then those of umpa_masked_grid_kernels.h.
+    int masked = 0;
 };
 
 // the block of umpa_grid_wide_match_region's host path: values, dbg_d, dbg_a, cover (doubles), then err, dbg_n (ints)
@@ -252,11 +257,31 @@ hipError_t widen_chunk(GridJob& J, const ModelDev& dev, const Maps& M, const Rep
     return hipGetLastError();
 }
 
+// the masked twins: a wave takes 64 pixels of one row (32: SequenceArgs::half), whatever R.bw_log2 says
+template <int KIND>
+void launch_masked_grid(const GridJob& J, const ModelDev& dev, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
+{
+    const dim3 grd((A.N1 + 63) / 64, R.rows), blk(64);
+    if (J.sequence) {
+        const int ls = 64 >> J.Q.half;
+        hipLaunchKernelGGL((masked_sequence_kernel<KIND>), dim3((A.N1 + ls - 1) / ls, R.rows), blk,
+                           sequence_lds(dev.ms, J.Q.prev != nullptr), s, dev, R, A, J.Q);
+    } else if (J.track) hipLaunchKernelGGL((masked_track_kernel<KIND>), grd, blk, grid_basins_lds(dev.ms), s, dev, R, A, J.K);
+    else if (J.basins) hipLaunchKernelGGL((masked_basins_kernel<KIND>), grd, blk, grid_basins_lds(dev.ms), s, dev, R, A, J.B);
+    else if (J.volume) hipLaunchKernelGGL((masked_volume_kernel<KIND>), grd, blk, 0, s, dev, R, A, J.V);
+    else hipLaunchKernelGGL((masked_min_kernel<KIND>), grd, blk, 0, s, dev, R, A);
+}
+
 // the consumer's kernel on the output rows R.rows of the table R, with the frame count as a template constant where
 // replay_walk's dispatch has it (tiled_match)
 hipError_t dispatch(const GridJob& J, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A, hipStream_t s)
 {
     if (R.rows <= 0 || A.N1 <= 0) return hipSuccess;
+    if (J.masked) {
+        if (J.masked == 3) launch_masked_grid<1>(J, dev, R, A, s);
+        else launch_masked_grid<0>(J, dev, R, A, s);
+        return hipGetLastError();
+    }
     const int kind = M.WS ? 1 : 0;
     const bool small = (size_t)M.H * M.W * 2 * sizeof(double) < ((size_t)1 << 32);   // a pair plane (tiled_match)
 #define UMPA_GRID_NA(n) case n: launch<1, n>(J, dev, M, R, A, s); break;
@@ -414,7 +439,7 @@ hipError_t consumer(void* user, const ModelDev& dev, const Maps& M0, const Repla
     Maps M = M0;
     ReplayArgs R = R0;
     RegionArgs A = A0;
-    const int kind = M.WS ? 1 : 0;
+    const int kind = J.masked ? (J.masked == 3 ? 1 : 0) : M.WS ? 1 : 0;
     if (J.L > 0) return levels_chunk(J, dev, M0, R0, A0, s);
     if (J.mhost) {
         const size_t n = (size_t)A.N0 * A.N1;
@@ -501,6 +526,11 @@ int run(umpa_hip_model* m, GridJob& J, int start0, int step0, int N0, int start1
         double* values, int nparam, int* err, const double* covermap, double thr,
         double* dbg_d, double* dbg_a, int* dbg_n, int flags, void* stream)
 {
+    J.masked = umpa_hipx_masked_table(m);
+    if (J.masked && (J.b > 0 || J.L > 0))
+        return fail(UMPA_HIP_E_UNSUPPORTED, "grid: window widening and scale space are not built for masked models: the table of a masked "
+                                            "model holds finished costs, and a finished cost is not linear in the windowed sums, so a box "
+                                            "average of costs is not the cost under a wider window");
     if (int rc = umpa_hipx_set_table_consumer(m, consumer, &J)) return fail(rc, "%s", umpa_hip_last_error());
     const int rc = umpa_hip_match_region(m, start0, step0, N0, start1, step1, N1, values, nparam, nullptr, err, covermap, thr,
                                          dbg_d, dbg_a, dbg_n, flags | UMPA_HIP_F_FORCE_TILED, stream);
@@ -833,6 +863,13 @@ int levels_track(umpa_hip_model* m, int start0, int step0, int N0, int start1, i
 } // namespace
 
 UMPA_GRID_API const char* umpa_grid_last_error(void) { return g_err.c_str(); }
+
+UMPA_GRID_API int umpa_grid_set_masked(umpa_hip_model* m, int on)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "grid: set_masked: null model");
+    if (int rc = umpa_hipx_set_masked_consumer(m, on)) return fail(rc, "%s", umpa_hip_last_error());
+    return 0;
+}
 
 UMPA_GRID_API int umpa_grid_match_region(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
                                          double* values, int nparam, double* uv, int* err,

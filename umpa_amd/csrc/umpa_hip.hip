@@ -452,6 +452,42 @@ bool tiled_applicable(const umpa_hip_model* m, const RegionArgs& A, bool forced 
     return tiled_supported(m->Nw, m->ms, m->Na);
 }
 
+// What keeps a masked model or a region off the masked tiled path by that path's own rules (tiled_applicable has the
+// reasons), as a text for a table consumer's refusal: those of them that UMPA_HIP_F_FORCE_TILED lifts, and those whose
+// refusal would otherwise not name its cause.  False: none of them applies.
+bool masked_consumer_refusal(const umpa_hip_model* m, const RegionArgs& A, char* why, size_t len)
+{
+    if (!masked_supported(m->Nw)) {
+        snprintf(why, len, "the masked table kernel has no configuration for window_size %d", m->Nw);
+        return true;
+    }
+    if (m->Na * (2 * m->Nw + 1) * (2 * m->Nw + 1) <= 9) {
+        snprintf(why, len, "exact-fit windows (frames x window pixels = %d <= 9): every cost is rounding noise around zero, "
+                           "and only the direct kernel sums in the reference's order", m->Na * (2 * m->Nw + 1) * (2 * m->Nw + 1));
+        return true;
+    }
+    if (m->kind == UMPA_HIP_KIND_DF) {
+        size_t Himg = 0, Wimg = 0;
+        for (int k = 0; k < m->Na; k++) {
+            Himg = std::max(Himg, (size_t)m->pos[2 * k] + m->dims[2 * k]); Wimg = std::max(Wimg, (size_t)m->pos[2 * k + 1] + m->dims[2 * k + 1]);
+        }
+        if (Himg * Wimg * 16 >= ((size_t)1 << 32)) {
+            snprintf(why, len, "a pair plane of the masked dark-field model (%zu x %zu pixels) passes 4 GiB", Himg, Wimg);
+            return true;
+        }
+    }
+    const int planes = (2 * m->ms - 1) * (2 * m->ms - 1);
+    const int base = m->kind == UMPA_HIP_KIND_NODF ? 16 : 5;
+    int lim = planes <= 81 ? base : base * 81 / planes;
+    if (lim < 1) lim = 1;
+    if (A.step0 * A.step1 > lim) {
+        snprintf(why, len, "steps %d x %d: the masked table is filled on the dense grid, its step limit is %d dense pixels per "
+                           "requested one (%d at up to 81 shifts, fewer beyond)", A.step0, A.step1, lim, base);
+        return true;
+    }
+    return false;
+}
+
 // Frames of one shape at different positions (sample stepping, Model.cpp:428-433 / :716-719): the image they tile,
 // the box of image rows / columns that lie inside every frame, and the rectangle [a0,b0) x [a1,b1) of region pixels
 // that every frame contributes to (coverage = Na there, so those pixels see exactly the all-frames sums the tiled
@@ -609,8 +645,16 @@ int run_match(umpa_hip_model* m, const RegionArgs& A, int flags, hipStream_t s,
     // (every rectangle with a constant set of contributing frames can go there, run_stepping_cells)
     const bool cells = can_tile && !whole && m->Na <= 32;
     const bool split = cells || (can_tile && !whole && (size_t)(g.b0 - g.a0) * (g.b1 - g.a1) * 2 >= (size_t)A.N0 * A.N1);
-    // a table consumer (umpa_hipx.h) takes the plain tiled path's table of the whole region, nothing else
-    if (m->tiled.consumer && !(whole && !m->has_mask && !(flags & UMPA_HIP_F_FORCE_DIRECT)))
+    // a masked model whose switch is on (umpa_hipx_set_masked_consumer): the consumer takes the masked path's table of
+    // finished costs, where that path takes the model and the region of its own accord -- UMPA_HIP_F_FORCE_TILED, which the
+    // consumers set, lifts the exact-fit gate and the step limit in tiled_applicable, so both are asked again here
+    if (m->tiled.consumer && m->has_mask && m->tiled.masked_consumer && m->kind != UMPA_HIP_KIND_DFKERNEL) {
+        char why[200];
+        if (masked_consumer_refusal(m, A, why, sizeof(why)))
+            return fail(UMPA_HIP_E_UNSUPPORTED, "a table consumer is set on a masked model (grid search / cost volume): %s", why);
+    }
+    // a table consumer (umpa_hipx.h) takes the tiled path's table of the whole region, nothing else
+    if (m->tiled.consumer && !(whole && (!m->has_mask || m->tiled.masked_consumer) && !(flags & UMPA_HIP_F_FORCE_DIRECT)))
         return fail(UMPA_HIP_E_UNSUPPORTED, "a table consumer is set (grid search / cost volume): the plain tiled path does not take "
                                             "this model and region whole (masks, frames at different positions, steps or search "
                                             "ranges past its limits, the kernel dark-field model, forced direct)");
@@ -1330,6 +1374,19 @@ int umpa_hipx_set_table_consumer(umpa_hip_model* m, umpa::TableConsumer fn, void
     if (!m) return fail(UMPA_HIP_E_ARG, "null model");
     m->tiled.consumer = fn; m->tiled.consumer_user = fn ? user : nullptr;
     return 0;
+}
+
+int umpa_hipx_set_masked_consumer(umpa_hip_model* m, int on)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "null model");
+    if (m->has_mask) m->tiled.masked_consumer = on != 0;
+    return 0;
+}
+
+int umpa_hipx_masked_table(const umpa_hip_model* m)
+{
+    if (!m || !m->has_mask || !m->tiled.masked_consumer || m->kind == UMPA_HIP_KIND_DFKERNEL) return 0;
+    return m->kind == UMPA_HIP_KIND_DF ? 3 : 2;
 }
 
 int umpa_hipx_set_stage_filter(umpa_hip_model* m, umpa_hipx_stage_filter fn, void* user, int H, int W, int device)

@@ -24,6 +24,19 @@ extern "C" {
 //     launch replay_walk.
 // With no consumer set every launch is what it was.  The caller clears it again, also after a failed match.
 int umpa_hipx_set_table_consumer(umpa_hip_model* m, umpa::TableConsumer fn, void* user);
+
+// The per-model switch of include/umpa_grid.h (umpa_grid_set_masked), off by default; it lives with the model and changes
+// nothing on a model without masks.  While it is on, a match of a masked model under a table consumer goes down the masked
+// tiled path whole (corr_masked, umpa_masked.h; on-demand stages off) and calls the consumer where it would launch
+// replay_cost, with a ReplayArgs that describes the chunk's table of FINISHED costs: [(2 ms - 1)^2][NV][drows][N1d] doubles,
+// slot_stride = drows * N1d, strip_w = 0; per slot the planes cost, T and (NV = 3: dark-field) v.  Maps holds what
+// tiled_match_masked filled (the reference means of the dark-field model, else nothing).  What that path does not take of
+// its own accord is UMPA_HIP_E_UNSUPPORTED with a text that names the reason: a window size without a corr_masked
+// configuration, exact-fit windows, a pair plane past 4 GiB, a step product past the masked limit.
+int umpa_hipx_set_masked_consumer(umpa_hip_model* m, int on);
+// NV of the table a consumer of `m` would be handed by the masked path (2, or 3 for the dark-field model); 0: the model has
+// no masks or its switch is off, the table is the plain path's.
+int umpa_hipx_masked_table(const umpa_hip_model* m);
 #endif
 
 // A stage filter takes the place of flat_correct_kernel in umpa_hip_stage_sample: frame k of the raw stack (k >= 0) lies in

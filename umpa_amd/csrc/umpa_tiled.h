@@ -499,6 +499,7 @@ typedef hipError_t (*TableConsumer)(void* user, const ModelDev& dev, const Maps&
 
 struct TiledState {
     TableConsumer consumer = nullptr;  void* consumer_user = nullptr;   // umpa_hipx_set_table_consumer
+    bool masked_consumer = false;      // umpa_hipx_set_masked_consumer: a consumer may be handed the masked path's table of finished costs
     double* maps = nullptr;   size_t maps_cap = 0;
     double* table = nullptr;  size_t table_cap = 0;
     bool table_limited = false;   // the budget's worth of table could not be allocated once: keep to the capacity we have
@@ -1442,6 +1443,18 @@ inline int tiled_match_masked(TiledState& st, const ModelDev& dev, int kind, int
         };
         auto replay = [&](const OdArgs& od) {
             if (rrows <= 0) return hipSuccess;
+            if (st.consumer) {                                        // the table of finished costs goes to the consumer's kernels (tiled_match)
+                ReplayArgs R;                                         // [(2ms-1)^2][NV][drows][N1d]: a slot is NV planes of slot_stride doubles
+                memset(&R, 0, sizeof(R));
+                R.table = st.table; R.slot_stride = MA.slot_stride; R.drow0 = drow0; R.N1d = N1d;
+                R.strip_w = 0; R.tw = 0; R.drows = drows;
+                R.row0 = xi_lo; R.rows = rrows;
+                R.bw_log2 = 4;
+                tt.tic(10);                                           // KN_CONSUMER (umpa_hip.hip), "table_consumer"
+                const hipError_t ce = st.consumer(st.consumer_user, dev, M, R, A, s);
+                tt.toc();
+                return ce;
+            }
             dim3 blk(64), grd((A.N1 + 15) / 16, (rrows + 3) / 4);           // blocks of 16 x 4 pixels (modes 0 and 2)
             if (od.mode == 3) grd = dim3(2 * device_cu_count(), 1);
             if (od.mode == 1) { grd = dim3((32 * od.tc + 63) / 64, od_seed_count(od.ntx, od.c0) * od_seed_count(od.nty, od.r0)); if (!grd.y) return hipSuccess; }
@@ -1451,7 +1464,8 @@ inline int tiled_match_masked(TiledState& st, const ModelDev& dev, int kind, int
             tt.toc();
             return hipGetLastError();
         };
-        return tiled_chunk(st, CL, od_enabled(E, ntiles, CL.npass, true) && !MA.ablate, (size_t)A.N0 * A.N1, s, tt, 6, corr, replay);
+        // (no on-demand stages while a table consumer is set: it reads every plane)
+        return tiled_chunk(st, CL, !st.consumer && od_enabled(E, ntiles, CL.npass, true) && !MA.ablate, (size_t)A.N0 * A.N1, s, tt, 6, corr, replay);
     });
 }
 

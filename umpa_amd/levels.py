@@ -144,6 +144,7 @@ def scale_space(model, levels=(4, 2, 1, 0), tol=None, lam=None, radius=None, ROI
     if not hasattr(model, "_grid_check"):
         raise RuntimeError("scale_space needs a model with track() (UMPAModelNoDF or UMPAModelDF)")
     model._grid_check("scale_space")
+    model._no_masked_widening("scale_space")
     levels = check_levels(levels)
     L = len(levels)
     tol = check_tol(tol, L)

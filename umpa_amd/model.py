@@ -385,11 +385,29 @@ class UMPAModelBase:
         return resolve_region(self._calculate_extent(), ROI, step, self._ROI)
 
     # -- coverage (model.pyx:499-529)
+    def _one_frame_box(self):
+        """All frames of one shape at position (0, 0)."""
+        sh0 = tuple(self._shape_list[0])
+        return all(tuple(p) == (0, 0) for p in self._pos_list) and all(tuple(s) == sh0 for s in self._shape_list)
+
     def _trivial_coverage(self):
         if self._mask is not None:
             return False
-        sh0 = tuple(self._shape_list[0])
-        return all(tuple(p) == (0, 0) for p in self._pos_list) and all(tuple(s) == sh0 for s in self._shape_list)
+        return self._one_frame_box()
+
+    def _masked_admitted(self):
+        """A model with masks whose ``masked_grid`` switch is on (a stub without the attribute counts as off)."""
+        return self._mask is not None and bool(getattr(self, "_masked_grid", False))
+
+    def _covered(self, s0, s1):
+        """``coverage >= thr`` on the region, with the threshold of ``match()`` (model.pyx:431): a numpy bool ``[N0, N1]``."""
+        covermap = self.coverage(ROI=(s0, s1))
+        return covermap >= .1 * covermap.max() / len(self._sam)
+
+    def _no_masked_widening(self, what):
+        if self._masked_admitted():
+            raise RuntimeError("%s: not available on a masked model: its table holds finished costs, and a finished cost is not "
+                               "linear in the windowed sums, so a box average of costs is not the cost under a wider window" % what)
 
     def coverage(self, step=None, ROI=None):
         s0, s1, N0, N1 = self._region(ROI, step)
@@ -416,6 +434,8 @@ class UMPAModelBase:
         grid = search == 'grid'
         if grid:
             self._grid_check("search='grid'")
+            if widen:
+                self._no_masked_widening("search='grid', widen=%d" % widen)
             if dxdy is not None:
                 raise RuntimeError("search='grid' looks at every shift of the search box: start shifts (dxdy) mean nothing to it")
         if (ROI is not None) and (step is not None):
@@ -530,9 +550,9 @@ class UMPAModelBase:
             why = "it runs on the HIP library only"
         elif self._kind == KIND_DFKERNEL:
             why = "the kernel dark-field model has no shift table"
-        elif self._mask is not None:
+        elif self._mask is not None and not self._masked_admitted():
             why = "masked models are not supported (their table holds finished costs)"
-        elif not self._trivial_coverage():
+        elif not self._one_frame_box():
             why = "frames at different positions (pos_list) or of different shapes are not supported"
         elif self._force & _lib.F_FORCE_DIRECT:
             why = "the model is forced onto the direct kernel"
@@ -547,6 +567,8 @@ class UMPAModelBase:
         and what comes back is the kept region (``widen_region``) and contiguous copies of its part of the arrays."""
         self._grid_check("cost_volume")
         widen = check_widen(widen)
+        if widen:
+            self._no_masked_widening("cost_volume, widen=%d" % widen)
         s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
         wide = widen_region(self._calculate_extent(), s0, s1, N0, N1, widen) if widen else None
         if wide:
@@ -571,6 +593,8 @@ class UMPAModelBase:
         s0, s1, out = self._grid_cost_volume(ROI, step, lambda U, N0, N1: {k: np.empty((U, U, N0, N1), dtype=NPDOUBLE) for k in keys}, widen)
         if widen:
             out['region'] = (s0, s1)
+        if self._masked_admitted():                                 # every pixel is computed: what match() would have skipped is marked
+            out['covered'] = self._covered(s0, s1)
         return out
 
     def _grid_basins(self, k, ROI, step, alloc, widen=0):
@@ -581,6 +605,8 @@ class UMPAModelBase:
         one-shot flag.  Returns ``(s0, s1, arrays)``.  ``widen`` as for ``_grid_cost_volume``."""
         self._grid_check("basins")
         widen = check_widen(widen)
+        if widen:
+            self._no_masked_widening("basins, widen=%d" % widen)
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not _lib.GRID_MIN_K <= k <= _lib.GRID_MAX_K:
             raise ValueError("basins: k must be an integer from %d to %d, not %r" % (_lib.GRID_MIN_K, _lib.GRID_MAX_K, k))
         k = int(k)
@@ -617,6 +643,8 @@ class UMPAModelBase:
         out['shift'] = np.stack([out.pop('si'), out.pop('sj')], axis=1)
         if widen:
             out['region'] = (s0, s1)
+        if self._masked_admitted():
+            out['covered'] = self._covered(s0, s1)
         return out
 
     def _grid_track(self, prior, mode, lam, radius, ROI, step, alloc, widen=0):
@@ -629,6 +657,8 @@ class UMPAModelBase:
         region, which go into NaN planes of the grown one (its other pixels have no basin anyway)."""
         self._grid_check("track")
         widen = check_widen(widen)
+        if widen:
+            self._no_masked_widening("track, widen=%d" % widen)
         s0, s1, N0, N1 = self._region(ROI, step, ROI_wins=True)
         wide = widen_region(self._calculate_extent(), s0, s1, N0, N1, widen) if widen else None
         if wide:
@@ -713,6 +743,8 @@ class UMPAModelBase:
         else:
             out['shift'] = np.stack([si, sj], axis=0)
             out['err'] = np.maximum(err, 0)
+        if self._masked_admitted():
+            out['covered'] = self._covered(s0, s1)
         return out
 
     def _grid_sequence(self, state, lam, trunc, ROI, step, alloc):
@@ -794,7 +826,7 @@ class UMPAModelBase:
             res.update({n: _lib.pinned_empty((N0, N1), np.int32) for n in ints})
             return res
 
-        _, _, res = self._grid_sequence(prev, lam, np.inf if trunc is None else trunc, ROI, step, alloc)
+        s0, s1, res = self._grid_sequence(prev, lam, np.inf if trunc is None else trunc, ROI, step, alloc)
         si, sj, err = res.pop('si'), res.pop('sj'), res.pop('err')
         if dev is not None:
             import torch
@@ -803,6 +835,8 @@ class UMPAModelBase:
         else:
             res['shift'] = np.stack([si, sj], axis=0)
             res['err'] = np.maximum(err, 0)
+        if self._masked_admitted():
+            res['covered'] = self._covered(s0, s1)
         return res
 
     _force = 0
@@ -1012,7 +1046,7 @@ class _UMPAModelPlain(UMPAModelBase):
     def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk', widen=0):
         """``search='walk'`` (default): the reference's minimiser.  ``search='grid'`` (extension): the global minimum over
         all ``(2 max_shift - 1)^2`` integer shifts, then the same sub-pixel step around it (``include/umpa_grid.h``);
-        plain models only (no masks, no ``pos_list``), no ``dxdy``.
+        no ``pos_list``, no ``dxdy``; a model with masks only with ``masked_grid`` switched on.
 
         ``widen=b`` (1 to 8, with ``search='grid'``; also on ``cost_volume``, ``basins`` and ``track``): window widening
         (``include/umpa_grid.h``).  The shift table and the maps are averaged over the ``(2b + 1)^2`` dense pixels around each
@@ -1036,7 +1070,9 @@ class _UMPAModelPlain(UMPAModelBase):
         ``max_shift=5`` -- so a ``ROI`` of the rows or the patch in question is the normal use.
 
         Models the plain tiled path takes whole only (no masks, no ``pos_list``, steps and search ranges within its
-        limits); anything else raises ``RuntimeError``.  ``widen``: as for ``match()``."""
+        limits); anything else raises ``RuntimeError``.  A model with masks is taken once ``masked_grid`` is switched on: every
+        pixel of the region is computed (NaN where a window has no pair weight) and the result has one more key,
+        ``covered``.  ``widen``: as for ``match()``; not on a masked model."""
         return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit, widen=widen)
 
     def basins(self, k=4, ROI=None, step=None, widen=0):
@@ -1112,6 +1148,28 @@ class _UMPAModelPlain(UMPAModelBase):
         """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
         from . import sigma
         return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step, sam=sam)
+
+
+    _masked_grid = False
+
+    @property
+    def masked_grid(self):
+        """The opt-in switch of the grid consumers for a model WITH masks (extension; ``include/umpa_grid.h``:
+        ``umpa_grid_set_masked``), ``False`` by default.  While it is ``False``, ``match(search='grid')``, ``cost_volume``,
+        ``basins``, ``track`` and ``sequence`` (and ``Tracker``, ``Sequence``, ``match_smooth``) refuse a masked model as they
+        always did.  Set to ``True``, they run on the masked tiled path's table of finished costs: ``match(search='grid')``
+        skips the pixels below the coverage threshold as ``match()`` does; the others compute every pixel and return one more
+        key, ``covered`` -- a numpy bool ``[N0, N1]``, ``coverage >= threshold`` with ``match()``'s threshold -- for the caller
+        to drop the rest.  ``widen > 0``, ``coarse_to_fine`` and ``scale_space`` stay refused: a finished cost is not linear in
+        the windowed sums.  On a model without masks the switch stays ``False`` and changes nothing."""
+        return bool(self._masked_grid)
+
+    @masked_grid.setter
+    def masked_grid(self, on):
+        on = bool(on) and self._mask is not None
+        if self._mask is not None:
+            _lib.grid().check(_lib.grid().set_masked(self._handle, int(on)), "grid set_masked")
+        self._masked_grid = on
 
 
 class UMPAModelNoDF(_UMPAModelPlain):

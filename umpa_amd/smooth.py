@@ -123,7 +123,7 @@ def match_smooth(model, lam=None, trunc=None, paths=8, ROI=None, step=None, quie
     ``model.match(dxdy=(start[0], start[1]), ROI=..., step=...)`` plus ``start`` (``[2, N0, N1]`` int32), ``margin``
     (``aggregate``), ``valid`` and the penalties used, ``lam`` and ``trunc``.
 
-    Models ``cost_volume()`` takes only (no masks, no ``pos_list``, not the kernel dark-field model): anything else
+    Models ``cost_volume()`` takes only (no ``pos_list``, not the kernel dark-field model, masks with ``masked_grid`` on): anything else
     raises what ``cost_volume()`` raises.  Mind the memory: four volumes of ``(2 max_shift - 1)^2 N0 N1`` doubles."""
     import torch
     _dirs(paths)

@@ -85,6 +85,8 @@ def coarse_to_fine(model, levels=(4, 2, 1, 0), radius=None, lam=None):
     levels = [_model.check_widen(b) for b in levels]
     if not levels:
         raise ValueError("coarse_to_fine: no levels")
+    if hasattr(model, "_no_masked_widening"):
+        model._no_masked_widening("coarse_to_fine")
     on_device = hasattr(model.sam_list[0], "data_ptr")
     results = []
     for n, b in enumerate(levels):
