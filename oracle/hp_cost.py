@@ -38,14 +38,14 @@ def _windows(stack, top, left, S):
 def hp_cells(kind, sam, ref, win, pi, pj, si, sj, assign="sam", mask=None):
     """Extended-precision cost, transmission, dark-field and the fp64 bound for n (pixel, shift) pairs: integer arrays
     ``pi, pj`` (image coordinates) and ``si, sj``.  All frames at position (0, 0), every frame contributes.
-    Returns a dict of longdouble arrays: cost, T, df (DF only), bound."""
+    Returns a dict of longdouble arrays: cost, T, df (DF only), bound, df_bound (DF only: the a-priori RELATIVE bound of df)."""
     sam, ref = np.asarray(sam, dtype=np.float64), np.asarray(ref, dtype=np.float64)
     K = sam.shape[0]
     S = win.shape[0]
     Nw = (S - 1) // 2
     pi, pj, si, sj = (np.asarray(v, dtype=np.int64).ravel() for v in (pi, pj, si, sj))
     w = np.asarray(win, dtype=np.float64).astype(LD)[None, None]
-    out = {k: [] for k in ("cost", "T", "df", "bound")}
+    out = {k: [] for k in ("cost", "T", "df", "bound", "df_bound")}
     for a in range(0, pi.size, CHUNK):
         i, j, di, dj = pi[a:a + CHUNK], pj[a:a + CHUNK], si[a:a + CHUNK], sj[a:a + CHUNK]
         if assign == "ref":                                   # lib/Model.cpp:408-421: the reference window stays
@@ -76,6 +76,16 @@ def hp_cells(kind, sam, ref, win, pi, pj, si, sj, assign="sam", mask=None):
             beta = (t3 * t4 - t5 * t6) / det
             T = beta + Kc
             out["df"].append(Kc / T)
+            # df = K / (beta + K) = N_K / (N_beta + N_K) with N_K = t2 t5 - t4 t6, N_beta = t3 t4 - t5 t6 (det cancels): where a
+            # numerator cancels -- df crosses zero, or the contrast is low -- no fp64 evaluation has a relative accuracy to be
+            # held to.  First order, any summation order, with the sums of |terms| for data of mixed sign:
+            a5, a4, a6 = (ww * np.abs(R * Q)).sum(axis=(1, 2, 3)), (np.abs(mean) * (ww * np.abs(Q)).sum(axis=(2, 3))).sum(axis=1), \
+                (np.abs(mean) * (ww * np.abs(R)).sum(axis=(2, 3))).sum(axis=1)
+            nk, nb = t2 * t5 - t4 * t6, t3 * t4 - t5 * t6
+            nu = (K * S * S + S * S + 8) * LD(2.0) ** -53
+            ek = nu * (t2 * np.abs(t5) + t2 * a5 + a4 * np.abs(t6) + np.abs(t4) * a6)
+            eb = nu * (t3 * np.abs(t4) + t3 * a4 + a5 * np.abs(t6) + np.abs(t5) * a6)
+            out["df_bound"].append(ek / np.abs(nk) + (ek + eb) / np.abs(nk + nb) + 3 * LD(2.0) ** -53)
             cost = (t1 + beta * beta * t2 + Kc * Kc * t3 - 2 * beta * t4 - 2 * Kc * t5 + 2 * beta * Kc * t6) / wt
             mag = np.abs(t1) + beta * beta * t2 + Kc * Kc * t3 + 2 * np.abs(beta * t4) + 2 * np.abs(Kc * t5) + 2 * np.abs(beta * Kc * t6)
         else:
