@@ -18,6 +18,8 @@
  *                           of the next, and per pixel the narrowest level that agrees with the wider ones ("scale space").
  *   umpa_grid_sequence      a per-pixel cost state over all shifts carried from projection to projection: each call adds its
  *                           costs to the cheapest compatible predecessor (forward dynamic programming, "sequence search").
+ *   umpa_grid_uncertainty   the uncertainty maps of include/umpa_sigma.h on the model's own device frames, masks included; it
+ *                           reads no table and runs no match (its own rules are at its declaration, not the paragraph below).
  *
  * All work on models that the plain tiled path takes whole: no masks, not the kernel dark-field model, all frames of
  * one shape at position (0, 0), steps and search ranges within that path's limits.  Anything else fails with
@@ -318,6 +320,97 @@ int umpa_grid_sequence(umpa_hip_model *m, int start0, int step0, int N0, int sta
                        double *f, double *T, double *dx, double *dy, double *cost, double *df,
                        int *si, int *sj, int *err, double *total, double *cost0, int *moved,
                        int flags, void *stream);
+
+/* Model-resident uncertainty: the per-pixel covariance of a matched shift and the noise estimate from the residual, computed
+ * on the MODEL'S OWN device frames -- no stack is passed and none is uploaded; masked models are admitted.
+ *
+ * The operation, its notation and its outputs are those of include/umpa_sigma.h (libumpa_sigma.so, which takes two bare stacks
+ * and never sees a model): the region rule, shift[2][N0][N1] with UMPA_SIGMA_SKIP, the PIXEL GUARD, FIELDS, MOMENTS, MODEL,
+ * SOLVE and OUTPUT.  sam, ref (and mask) are the model's frames, win its window, Nw, ms = max_shift and pad = its padding.  The
+ * sample stack is the one the LAST MATCH ADOPTED: after umpa_hip_stage_sample and a match with UMPA_HIP_F_USE_STAGED that is
+ * the staged, flat-corrected stack; a stack staged and not yet adopted is not read, and this call takes no
+ * UMPA_HIP_F_USE_STAGED.  kind: 0 for UMPA_HIP_KIND_NODF, 1 for UMPA_HIP_KIND_DF.
+ *
+ * A model WITHOUT masks: the definition is include/umpa_sigma.h's, unchanged and not restated: P = 16 / 34 planes, their
+ * rounding bound, dof = K - tr.  Fed the same frames and shifts, the moments agree with umpa_sigma_region's within that bound.
+ *
+ * A model WITH masks (no switch: umpa_grid_set_masked is not needed).  The pair weight of the matchers' cost enters the window
+ * weight and is held fixed at the integer shift; it is not differentiated.
+ * FIELDS per frame k and tap x, in addition to a, r, g_i, g_j, u = (u_0, u_1, u_2) = (g_i, g_j, r) of include/umpa_sigma.h:
+ *     p = mask[k] at the reference tap (where r is read)        q = mask[k] at the sample tap (where a is read)
+ *     c = (p * q) / ((p + q) + 1e-8)                            (the reference's combine_weights)
+ *     w = c * win[x]                                            v = w * w
+ *   per frame, sum_x in tap order:
+ *     omega = sum_x w              nu  = sum_x v                 (plain additions)
+ *     m_p   = sum_x w u_p          n_p = sum_x v u_p             m_a = sum_x w a        (each term one product, plain additions)
+ *     mu_p  = (sum_x win[x] u_p) / win_sum        dark-field only; each term one fma(win[x], u_p, sum); win_sum: the window
+ *             summed in tap order in doubles.  This is the UNMASKED windowed mean of the reference, as in the masked cost
+ *             function of the reference, and (p = 0, 1) its central differences.
+ * MOMENTS, [P][N0][N1] planes, P = UMPA_GRID_SIGMA_PLANES_PLAIN = 17 or UMPA_GRID_SIGMA_PLANES_DF = 50; every accumulation
+ * into a plane is one fma(first factor, last factor, plane), the first factor a rounded product where it is bracketed:
+ *      0 ..  5   S_pq  = sum_k sum_x (w u_p) u_q        (p, q) = 00 01 02 11 12 22
+ *      6 .. 11   V_pq  = sum_k sum_x (v u_p) u_q        same order
+ *     12 .. 14   P_p   = sum_k sum_x (w a) u_p          p = 0 1 2
+ *     15         Q     = sum_k sum_x (w a) a
+ *     16         W     = sum_k omega                    (a plain addition per frame)
+ *   dark-field only:
+ *     17 .. 25   MU_pq = sum_k m_p mu_q                 (p, q) = 00 01 02 10 11 12 20 21 22
+ *     26 .. 31   WM_pq = sum_k (omega mu_p) mu_q        (p, q) = 00 01 02 11 12 22
+ *     32 .. 40   NU_pq = sum_k n_p mu_q                 nine as MU
+ *     41 .. 46   VM_pq = sum_k (nu mu_p) mu_q           six as WM
+ *     47 .. 49   AU_p  = sum_k m_a mu_p                 p = 0 1 2
+ * S, V, WM, VM are symmetric.  ROUNDING BOUND of a double evaluation, u = 2^-53, T = (2 Nw + 1)^2, derived as the sibling's:
+ *     planes 0 .. 16:   (K T + 16) u sum |term|        (c: 4 roundings -- p q, p + q, + 1e-8, the division; w: 1 more, 5 in
+ *                                                      all; v = w w: 2 x 5 + 1 = 11; the two differences g: 2; at most 2
+ *                                                      products: 15 for the worst term, a V_pq; K T additions; 1 to spare.
+ *                                                      W: its terms are w, 5 roundings and T + K additions)
+ *     planes 17 .. 49:  (3 T + K + 20) u sum_k of the product of the factors' sums of absolute terms
+ *                                                     (the worst plane, VM: nu: T additions and 11 roundings per term; each
+ *                                                      mu: T additions, at most 2 roundings per term and the division by
+ *                                                      win_sum, which is the double both evaluations divide by, T + 3;
+ *                                                      2 products; K additions: 3 T + K + 19; 1 to spare.  The factors'
+ *                                                      sums: sum_x |w' u_p| with w' = w or v, sum_x |w a|, sum_x w, sum_x v,
+ *                                                      (sum_x |win[x] u_q|) / win_sum)
+ * MODEL at the shift.
+ *     plain        as include/umpa_sigma.h: T = P_2 / S_22 and A, B, h, rss0 of its plain model, from the planes 0 .. 15.
+ *     dark-field   a ~ beta mu_2 + Kc r, with t1 = Q, t2 = WM_22, t3 = S_22, t4 = AU_2, t5 = P_2, t6 = MU_22 (the sums t1 .. t6
+ *                  of the matchers' masked cost function) and det, Kc, beta, rss0 the sibling's expressions in t1 .. t6.
+ *                  theta = (delta_i, delta_j, beta, Kc)      J = (Kc g_i + beta mu_0, Kc g_j + beta mu_1, mu_2, r)
+ *                  e = a - beta mu_2 - Kc r.   With p, q in {0, 1}, KK = Kc * Kc, kb = Kc * beta, bb = beta * beta:
+ *         A_pq = (KK * S_pq + kb * (MU_pq + MU_qp)) + bb * WM_pq
+ *         A_p2 = Kc * MU_p2 + beta * WM_p2             A_p3 = Kc * S_p2 + beta * MU_2p
+ *         A_22 = WM_22        A_23 = MU_22             A_33 = S_22
+ *         B is A with V, NU, VM in place of S, MU, WM:
+ *         B_pq = (KK * V_pq + kb * (NU_pq + NU_qp)) + bb * VM_pq
+ *         B_p2 = Kc * NU_p2 + beta * VM_p2             B_p3 = Kc * V_p2 + beta * NU_2p
+ *         B_22 = VM_22        B_23 = NU_22             B_33 = V_22
+ *         h_p  = Kc * ((P_p - beta * MU_p2) - Kc * S_p2) + beta * ((AU_p - beta * WM_p2) - Kc * MU_2p)
+ *         h_2  = (AU_2 - beta * WM_22) - Kc * MU_22    h_3  = (P_2 - beta * MU_22) - Kc * S_22
+ * SOLVE is include/umpa_sigma.h's, word for word, with one change:  dof = W - tr.  The expected weighted residual per unit
+ * noise variance is tr(diag w) - tr(A^-1 B); with weights that sum to 1 per frame that is K - tr, with pair weights it is W - tr.
+ * OUTPUT as include/umpa_sigma.h.  A window without any pair weight has all moments 0: T (Kc, beta) is 0 / 0, the first pivot
+ * is NaN, hence BAD: valid = 0 and NaN outputs.  A NaN pixel under a zero weight still poisons every window that holds it
+ * (0 * NaN), as it poisons the reference's masked cost.
+ * Everything after the moments is fp64 + - * / in the order written, without contraction.
+ *
+ * Arrays: shift 2 * N0 * N1 ints (read); moments P * N0 * N1 doubles or NULL; unit 3 * N0 * N1 doubles; s2, dof N0 * N1
+ * doubles; valid N0 * N1 ints.  Host arrays by default: the shift field is uploaded and the results are downloaded, the frames
+ * stay where they are.  With UMPA_HIP_F_DEVICE_IO they are device arrays on the model's device and the kernel runs on `stream`.
+ * Either way the call is ordered after everything the model has enqueued on any stream (it waits for the model's device
+ * first) and returns when the results are written.
+ * UMPA_HIP_E_ARG, before anything touches a device: a NULL model, shift, unit, s2, dof or valid; a flag other than
+ * UMPA_HIP_F_DEVICE_IO; N < 1, step < 1 or start < 0 on either axis.  UMPA_HIP_E_ARG, before any kernel is launched or memory
+ * allocated (the extent is the model's): start + step (N - 1) > H - 2 pad - 1 (resp. W).
+ * UMPA_HIP_E_UNSUPPORTED, before any kernel is launched, with a text that names the reason and the values: the kernel
+ * dark-field model; frames of unequal shapes or at non-zero positions; a reference-coordinate model (ref_mode != 0); Nw
+ * outside 1 .. 8; padding != Nw + max_shift; a window that is not finite, non-negative and normalised (|sum win - 1| <= 1e-9).
+ * One lane per pixel, one writer per output, no atomics: the output is the same bit for bit from run to run and for host and
+ * device arrays. */
+#define UMPA_GRID_SIGMA_PLANES_PLAIN 17
+#define UMPA_GRID_SIGMA_PLANES_DF 50
+int umpa_grid_uncertainty(umpa_hip_model *m, int start0, int step0, int N0, int start1, int step1, int N1,
+                          const int *shift, double *moments, double *unit, double *s2, double *dof, int *valid,
+                          int flags, void *stream);
 
 const char *umpa_grid_last_error(void);
 

@@ -6,6 +6,8 @@
 // feature code.  A call sets itself as the model's table
 // consumer (umpa_hipx.h), runs umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
+// One call is no table consumer: umpa_grid_uncertainty (umpa_resident_kernels.h, at the end of this file) runs one kernel on the
+// model's own device frames, which umpa_hipx_model_view lends it.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <string>
@@ -20,6 +22,7 @@
 #include "umpa_levels_kernels.h"
 #include "umpa_sequence_kernels.h"
 #include "umpa_masked_grid_kernels.h"
+#include "umpa_resident_kernels.h"
 
 using namespace umpa;
 
@@ -964,4 +967,124 @@ UMPA_GRID_API int umpa_grid_levels_track(umpa_hip_model* m, int start0, int step
     const LevelsPlanes lev = {f, T, dx, dy, cost, df, cost0, si, sj, err, count, found};
     const LevelsPlanes sel = {sel_f, sel_T, sel_dx, sel_dy, sel_cost, sel_df, sel_cost0, sel_si, sel_sj, sel_err, sel_count, sel_found};
     return levels_track(m, start0, step0, N0, start1, step1, N1, L, b, mode, lam, radius, tol, lev, sel, level, halfwidth, flags, stream);
+}
+
+// Model-resident uncertainty (umpa_resident_kernels.h): no table, no match -- one kernel on the model's own device frames.
+namespace {
+
+// sv of include/umpa_sigma.h: the squares of the window summed in tap order, as two roundings per tap
+double resident_sv(const double* win, int T)
+{
+    volatile double sv = 0.0;                       // (volatile: no contraction of w * w + sv, whatever the host flags)
+    for (int x = 0; x < T; x++) { volatile double v = win[x] * win[x]; sv = sv + v; }
+    return sv;
+}
+
+int resident_axis(const char* name, int start, int step, int N, int extent)
+{
+    if (N < 1 || step < 1 || start < 0 || (long long)start + (long long)step * (N - 1) > (long long)extent - 1)
+        return fail(UMPA_HIP_E_ARG, "grid: uncertainty: region axis %s: start %d, step %d, %d pixels exceed the extent %d", name, start, step, N, extent);
+    return 0;
+}
+
+void resident_launch(int kind, bool masked, const ModelDev& dev, const ResidentArgs& a, hipStream_t s)
+{
+    const dim3 grd((a.N1 + RESIDENT_TILE_X - 1) / RESIDENT_TILE_X, (a.N0 + RESIDENT_TILE_Y - 1) / RESIDENT_TILE_Y), blk(RESIDENT_TILE_X, RESIDENT_TILE_Y);
+    if (kind && masked) hipLaunchKernelGGL((resident_moments_kernel<1, true>), grd, blk, 0, s, dev, a);
+    else if (kind) hipLaunchKernelGGL((resident_moments_kernel<1, false>), grd, blk, 0, s, dev, a);
+    else if (masked) hipLaunchKernelGGL((resident_moments_kernel<0, true>), grd, blk, 0, s, dev, a);
+    else hipLaunchKernelGGL((resident_moments_kernel<0, false>), grd, blk, 0, s, dev, a);
+}
+
+} // namespace
+
+UMPA_GRID_API int umpa_grid_uncertainty(umpa_hip_model* m, int start0, int step0, int N0, int start1, int step1, int N1,
+                                        const int* shift, double* moments, double* unit, double* s2, double* dof, int* valid,
+                                        int flags, void* stream)
+{
+    if (!m || !shift || !unit || !s2 || !dof || !valid)
+        return fail(UMPA_HIP_E_ARG, "grid: uncertainty: null argument (the model, shift, unit, s2, dof and valid are required)");
+    if (flags & ~UMPA_HIP_F_DEVICE_IO) return fail(UMPA_HIP_E_ARG, "grid: uncertainty takes UMPA_HIP_F_DEVICE_IO and no other flag");
+    if (int rc = resident_axis("0", start0, step0, N0, 1 << 30)) return rc;       // N, step, start; the extent below
+    if (int rc = resident_axis("1", start1, step1, N1, 1 << 30)) return rc;
+    ModelDev dev;
+    int mkind = 0, has_mask = 0, device = 0;
+    hipStream_t ms = nullptr;
+    if (int rc = umpa_hipx_model_view(m, &dev, &mkind, &has_mask, &device, &ms)) return fail(rc, "grid: uncertainty: %s", umpa_hip_last_error());
+    // what the host knows of the model
+    if (mkind != UMPA_HIP_KIND_NODF && mkind != UMPA_HIP_KIND_DF)
+        return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: the kernel dark-field model (kind %d) is not supported", mkind);
+    if (dev.ref_mode != 0)
+        return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: a reference-coordinate model (ref_mode = %d) is not supported", dev.ref_mode);
+    if (dev.Nw < 1 || dev.Nw > RESIDENT_MAX_NW)
+        return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: Nw = %d (1 to %d are supported)", dev.Nw, RESIDENT_MAX_NW);
+    if (dev.ms < 1 || dev.padding != dev.Nw + dev.ms)
+        return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: padding = %d, Nw + max_shift = %d + %d (a window narrower than the model was "
+                                            "built with is not supported)", dev.padding, dev.Nw, dev.ms);
+    if (dev.Na < 1 || dev.Na > (1 << 20)) return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: a model of %d frames", dev.Na);
+    HIPOK(hipSetDevice(device), UMPA_HIP_E_DEVICE, "grid: uncertainty: hipSetDevice(%d)", device);
+    // after everything the model has enqueued, on whatever stream: the descriptor table is rewritten in stream order by the
+    // call that adopts a staged stack, and the frames may still be written by an upload
+    HIPOK(hipDeviceSynchronize(), UMPA_HIP_E_DEVICE, "grid: uncertainty: waiting for the model's work");
+    const int side = 2 * dev.Nw + 1, T = side * side, pad = dev.padding;
+    std::vector<FrameDesc> desc((size_t)dev.Na);
+    double win[(2 * RESIDENT_MAX_NW + 1) * (2 * RESIDENT_MAX_NW + 1)];
+    HIPOK(hipMemcpy(desc.data(), dev.frames, (size_t)dev.Na * sizeof(FrameDesc), hipMemcpyDeviceToHost), UMPA_HIP_E_DEVICE, "grid: uncertainty: the frame table");
+    HIPOK(hipMemcpy(win, dev.win, (size_t)T * sizeof(double), hipMemcpyDeviceToHost), UMPA_HIP_E_DEVICE, "grid: uncertainty: the window");
+    const int H = desc[0].H, W = desc[0].W;
+    for (int k = 0; k < dev.Na; k++) {
+        const FrameDesc& f = desc[k];
+        if (f.H != H || f.W != W || f.pi != 0 || f.pj != 0)
+            return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: frame %d has %d x %d pixels at (%d, %d), frame 0 %d x %d at (0, 0): frames at "
+                                                "different positions or of different shapes are not supported", k, f.H, f.W, f.pi, f.pj, H, W);
+        if (!f.sam || !f.ref || (has_mask && !f.mask)) return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: frame %d has no device frames", k);
+    }
+    if (H < 2 * pad + 1 || W < 2 * pad + 1)
+        return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: frames of %d x %d pixels (at least %d x %d for padding %d)", H, W, 2 * pad + 1, 2 * pad + 1, pad);
+    double sw = 0.0;
+    for (int x = 0; x < T; x++) {
+        if (!(win[x] >= 0.0) || !std::isfinite(win[x]))
+            return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: window entry %d is %g (finite and >= 0)", x, win[x]);
+        sw += win[x];
+    }
+    if (!(std::fabs(sw - 1.0) <= 1e-9))
+        return fail(UMPA_HIP_E_UNSUPPORTED, "grid: uncertainty: the window sums to %.17g (it must be normalised)", sw);
+    if (int rc = resident_axis("0", start0, step0, N0, H - 2 * pad)) return rc;
+    if (int rc = resident_axis("1", start1, step1, N1, W - 2 * pad)) return rc;
+
+    const bool dio = (flags & UMPA_HIP_F_DEVICE_IO) != 0, masked = has_mask != 0;
+    const int kind = mkind == UMPA_HIP_KIND_DF ? 1 : 0;
+    const size_t n = (size_t)N0 * N1;
+    const int P = masked ? (kind ? UMPA_GRID_SIGMA_PLANES_DF : UMPA_GRID_SIGMA_PLANES_PLAIN) : (kind ? 34 : 16);
+    hipStream_t s = dio ? (hipStream_t)stream : ms;
+    ResidentArgs a;
+    a.H = H; a.W = W; a.sv = resident_sv(win, T);
+    a.start0 = start0; a.step0 = step0; a.N0 = N0; a.start1 = start1; a.step1 = step1; a.N1 = N1;
+    a.shift = shift; a.moments = moments; a.unit = unit; a.s2 = s2; a.dof = dof; a.valid = valid;
+    if (dio) {
+        resident_launch(kind, masked, dev, a, s);
+        LAUNCHED("grid: uncertainty: launch of the moments kernel");
+        HIPOK(hipStreamSynchronize(s), UMPA_HIP_E_LAUNCH, "grid: uncertainty");
+        return 0;
+    }
+    // host arrays: slots 0 shift, 1 moments, 2 unit, 3 s2, 4 dof, 5 valid
+    DeviceMem S;
+    const size_t bytes[5] = {moments ? P * n * 8 : 0, 3 * n * 8, n * 8, n * 8, n * 4};
+    void* host[5] = {moments, unit, s2, dof, valid};
+    HIPOK(S.alloc(0, 2 * n * 4), UMPA_HIP_E_NOMEM, "grid: uncertainty: device memory for the shift field");
+    for (int q = 0; q < 5; q++)
+        if (host[q]) HIPOK(S.alloc(1 + q, bytes[q]), UMPA_HIP_E_NOMEM, "grid: uncertainty: device memory for the results");
+    HIPOK(hipMemcpyAsync(S.p[0], shift, 2 * n * 4, hipMemcpyHostToDevice, s), UMPA_HIP_E_DEVICE, "grid: uncertainty: upload of the shift field");
+    a.shift = (const int*)S.p[0]; a.moments = (double*)S.p[1]; a.unit = (double*)S.p[2]; a.s2 = (double*)S.p[3]; a.dof = (double*)S.p[4];
+    a.valid = (int*)S.p[5];
+    resident_launch(kind, masked, dev, a, s);
+    const hipError_t le = hipGetLastError();
+    hipError_t e = le;
+    for (int q = 0; q < 5 && e == hipSuccess; q++)
+        if (host[q]) e = hipMemcpyAsync(host[q], S.p[1 + q], bytes[q], hipMemcpyDeviceToHost, s);
+    const hipError_t se = hipStreamSynchronize(s);       // nothing of this call may still use the memory freed on return
+    if (le != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "grid: uncertainty: launch of the moments kernel: %s", hipGetErrorString(le));
+    if (e != hipSuccess) return fail(UMPA_HIP_E_DEVICE, "grid: uncertainty: download of the results: %s", hipGetErrorString(e));
+    if (se != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "grid: uncertainty: %s", hipGetErrorString(se));
+    return 0;
 }

@@ -1389,6 +1389,13 @@ int umpa_hipx_masked_table(const umpa_hip_model* m)
     return m->kind == UMPA_HIP_KIND_DF ? 3 : 2;
 }
 
+int umpa_hipx_model_view(umpa_hip_model* m, umpa::ModelDev* dev, int* kind, int* has_mask, int* device, hipStream_t* stream)
+{
+    if (!m || !dev || !kind || !has_mask || !device || !stream) return fail(UMPA_HIP_E_ARG, "null argument");
+    *dev = m->dev(); *kind = m->kind; *has_mask = m->has_mask ? 1 : 0; *device = m->device; *stream = m->stream;
+    return 0;
+}
+
 int umpa_hipx_set_stage_filter(umpa_hip_model* m, umpa_hipx_stage_filter fn, void* user, int H, int W, int device)
 {
     if (!m) return fail(UMPA_HIP_E_ARG, "null model");

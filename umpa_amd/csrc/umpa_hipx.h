@@ -37,6 +37,15 @@ int umpa_hipx_set_masked_consumer(umpa_hip_model* m, int on);
 // NV of the table a consumer of `m` would be handed by the masked path (2, or 3 for the dark-field model); 0: the model has
 // no masks or its switch is off, the table is the plain path's.
 int umpa_hipx_masked_table(const umpa_hip_model* m);
+
+// The model as its own kernels see it (umpa_grid_uncertainty runs a kernel of libumpa_grid.so on the model's device frames):
+// `*dev` is the model's ModelDev -- the descriptor table (per frame sam, ref, mask, shape and position), the window and its
+// sum, Na, Nw, max_shift, padding, ref_mode -- `*kind` UMPA_HIP_KIND_*, `*has_mask` 0 or 1, `*device` its device, `*stream`
+// the stream of its host-array entry points.  The sample pointers are those of the stack the LAST MATCH ADOPTED: a stack
+// that umpa_hip_stage_sample uploaded and no call has adopted yet is not it, and this call takes no UMPA_HIP_F_USE_STAGED.
+// The descriptor table is rewritten in stream order by the call that adopts a staged stack: a caller that reads it on another
+// stream waits for the model's work first.  Host code only: nothing is enqueued.  UMPA_HIP_E_ARG for a NULL argument.
+int umpa_hipx_model_view(umpa_hip_model* m, umpa::ModelDev* dev, int* kind, int* has_mask, int* device, hipStream_t* stream);
 #endif
 
 // A stage filter takes the place of flat_correct_kernel in umpa_hip_stage_sample: frame k of the raw stack (k >= 0) lies in

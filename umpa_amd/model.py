@@ -883,7 +883,7 @@ class UMPAModelBase:
         The staged stack becomes the sample stack of the next call that reads the sample stack -- ``match()``,
         ``cost_volume()``, ``basins()``, ``track()``, ``sequence()``, ``match_smooth`` -- and stays it.  The last stack wins: another ``stage_sample`` or
         ``update_frames(sam_list=...)`` before that call replaces it.  The model keeps no host copy of a staged stack:
-        ``uncertainty()`` then needs it as ``sam=``."""
+        ``uncertainty()`` then needs it as ``sam=``, or ``resident=True``, which reads the adopted stack on the device."""
         if not self._lib.is_hip or hasattr(self._sam[0], "data_ptr"):
             raise RuntimeError('stage_sample needs a model that owns device copies of host frames.')
         raw = [np.asarray(x) for x in raw_frames]
@@ -1144,10 +1144,11 @@ class _UMPAModelPlain(UMPAModelBase):
         series on the device."""
         return self._sequence(state=state, lam=lam, trunc=trunc, ROI=ROI, step=step, out=out)
 
-    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
-        """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``."""
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None, resident=False, shift=None):
+        """The per-pixel uncertainty maps of ``result = self.match(...)`` (extension): ``umpa_amd.sigma.uncertainty``.
+        ``resident=True``: on the model's own device frames -- masked models, staged stacks, no upload."""
         from . import sigma
-        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step, sam=sam)
+        return sigma.uncertainty(self, result, noise_var=noise_var, ROI=ROI, step=step, sam=sam, resident=resident, shift=shift)
 
 
     _masked_grid = False
@@ -1229,5 +1230,5 @@ class UMPAModelDFKernel(UMPAModelBase):
                              num_threads=num_threads, quiet=quiet)
         return self._unpack(result, False)
 
-    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None):
+    def uncertainty(self, result, noise_var=None, ROI=None, step=None, sam=None, resident=False, shift=None):
         raise RuntimeError("uncertainty: the kernel dark-field model is not supported")

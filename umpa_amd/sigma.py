@@ -7,12 +7,15 @@ what any least-squares estimator offers: the covariance of the estimated shift f
 integer shift -- in the sandwich form, because the window weights are not inverse variances -- and a noise estimate from
 the residual after a linearised sub-pixel refit.  ``Uncertainty.weight()`` is an inverse-variance weight for
 ``phase_from_match(result, weight=...)``.  HIP only: there is no CPU fallback.
+
+``uncertainty(..., resident=True)`` and ``resident`` run the same operation on the model's own device frames
+(``umpa_grid_uncertainty`` of ``libumpa_grid.so``, ``include/umpa_grid.h``): no upload, staged stacks, masked models.
 """
 import numpy as np
 
 from . import _lib
 
-__all__ = ["region", "solve", "shift_field", "uncertainty", "Uncertainty", "SKIP"]
+__all__ = ["region", "solve", "resident", "shift_field", "uncertainty", "Uncertainty", "SKIP"]
 
 SKIP = _lib.SIGMA_SKIP                 # the shift of a pixel that is to be skipped (any value outside +-(max_shift - 1) is)
 
@@ -138,17 +141,18 @@ class Uncertainty:
         return np.where(self.valid & np.isfinite(w), w, 0.0)
 
 
-def _check_model(model):
-    """What the definition does not cover is refused here by name."""
+def _check_model(model, resident=False):
+    """What the definition does not cover is refused here by name.  ``resident``: the call on the model's own device frames
+    (``umpa_grid_uncertainty``), which takes masks."""
     from . import model as M
     why = None
     if not model._lib.is_hip:
         why = "it runs on the HIP library only"
     elif model._kind == M.KIND_DFKERNEL:
         why = "the kernel dark-field model is not supported"
-    elif model._mask is not None:
+    elif model._mask is not None and not resident:
         why = "masked models are not supported"
-    elif not model._trivial_coverage():
+    elif not (model._one_frame_box() if resident else model._trivial_coverage()):
         why = "frames at different positions (pos_list) or of different shapes are not supported"
     elif model._refshift != 0:
         why = "assign_coordinates='ref' is not supported"
@@ -197,7 +201,51 @@ def _given_stack(model, sam):
     return sam
 
 
-def uncertainty(model, result, noise_var=None, ROI=None, step=None, sam=None):
+def resident(model, area, shift, moments=False):
+    """``umpa_grid_uncertainty`` (``include/umpa_grid.h``): ``region`` on the model's own device frames -- the sample stack
+    the last match adopted, the reference stack, the masks of a masked model, its window -- without passing or uploading a
+    stack.  ``area``: ``(start0, step0, N0, start1, step1, N1)``; ``shift``: ``[2, N0, N1]`` int32, a host array (host arrays
+    come back) or a contiguous HIP tensor on the model's device (HIP tensors come back, computed on the current stream).
+    ``moments``: also the ``[P, N0, N1]`` planes, ``P`` = 16 / 34 without masks, 17 / 50 with."""
+    start0, step0, N0, start1, step1, N1 = (int(v) for v in area)
+    if N0 < 1 or N1 < 1:
+        raise ValueError("an empty region: %d x %d pixels" % (N0, N1))
+    kind = int(model._kind)
+    P = (_lib.GRID_SIGMA_PLANES if model._mask is not None else _lib.SIGMA_PLANES)[kind]
+    lib = _lib.grid()
+    io = _lib.Side(shift, device=model._device)
+    if io.on_device:
+        import torch
+        if shift.dtype != torch.int32:
+            raise ValueError("shift must be int32, not %s" % shift.dtype)
+        if not shift.is_cuda or shift.device.index != model._device:
+            raise ValueError("shift must be a host array or a HIP tensor on the model's device %d, not on %s" % (model._device, shift.device))
+    else:
+        shift = np.ascontiguousarray(shift, dtype=np.int32)
+    if tuple(shift.shape) != (2, N0, N1):
+        raise ValueError("shift must be [2, %d, %d], not %r" % (N0, N1, tuple(shift.shape)))
+    _, flags, stream = io.tail()
+    out = _outputs(io, (N0, N1), (P, N0, N1) if moments else None)
+    rc = lib.uncertainty(model._handle, start0, step0, N0, start1, step1, N1, io.ptr(shift),
+                         *[io.ptr(out.get(k)) for k in ("moments", "unit", "s2", "dof", "valid")], flags, stream)
+    lib.check(rc, "grid uncertainty")
+    return out
+
+
+def _uncertainty_resident(model, result, noise_var, ROI, step, shift):
+    """``uncertainty(..., resident=True)``: no stacking, no upload of frames; the outputs are numpy as ever."""
+    s0, s1, N0, N1 = model._region(ROI, step, ROI_wins=True)
+    if tuple(np.shape(result["dx"])) != (N0, N1):
+        raise ValueError("the maps of result are %r, the region has %d x %d pixels" % (tuple(np.shape(result["dx"])), N0, N1))
+    if shift is None:
+        shift = shift_field(result, model._max_shift)
+    out = resident(model, (s0[0], s0[2], N0, s1[0], s1[2], N1), shift)
+    if hasattr(shift, "data_ptr"):
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+    return Uncertainty(out["unit"], out["s2"], out["dof"], out["valid"], noise_var)
+
+
+def uncertainty(model, result, noise_var=None, ROI=None, step=None, sam=None, resident=False, shift=None):
     """The uncertainty maps of ``result = model.match(...)``: an ``Uncertainty``.
 
     The model supplies its stacks and its window (host frames are uploaded by the call, HIP tensors are read where they
@@ -209,10 +257,24 @@ def uncertainty(model, result, noise_var=None, ROI=None, step=None, sam=None):
     ``sigma_sam^2 + T^2 sigma_ref^2``, where it is known; by default the variances are scaled with ``s2``, which at low noise
     also contains interpolation and model misfit and is then an upper estimate.
 
-    Plain and dark-field models without masks or ``pos_list``, ``assign_coordinates='sam'``."""
-    _check_model(model)
+    Plain and dark-field models without masks or ``pos_list``, ``assign_coordinates='sam'``.
+
+    ``resident=True`` computes the maps on the model's own device frames instead (``umpa_grid_uncertainty``,
+    ``include/umpa_grid.h``): nothing is stacked and no frame is uploaded, so it also works after ``stage_sample`` -- the
+    stack is the one the last match adopted -- and on a model WITH masks, where the pair weight of the cost function enters
+    the window weight and ``dof`` is the weight sum minus the trace.  ``sam=`` is then an error.  ``shift``: an int32
+    ``[2, N0, N1]`` host array or HIP tensor on the model's device to use in place of ``shift_field(result)``, e.g. the stacked
+    ``(si, sj)`` of ``basins`` / ``track`` / ``sequence``; it needs ``resident=True``.  Without ``resident`` the call is what
+    it always was."""
+    _check_model(model, resident=bool(resident))
     if noise_var is not None and not (np.isfinite(noise_var) and noise_var >= 0 and np.ndim(noise_var) == 0):
         raise ValueError("noise_var must be a finite scalar >= 0, not %r" % (noise_var,))
+    if resident:
+        if sam is not None:
+            raise ValueError("uncertainty: resident=True reads the model's own device frames; sam= cannot be given with it")
+        return _uncertainty_resident(model, result, noise_var, ROI, step, shift)
+    if shift is not None:
+        raise ValueError("uncertainty: shift= needs resident=True")
     s0, s1, N0, N1 = model._region(ROI, step, ROI_wins=True)
     if tuple(np.shape(result["dx"])) != (N0, N1):
         raise ValueError("the maps of result are %r, the region has %d x %d pixels" % (tuple(np.shape(result["dx"])), N0, N1))
