@@ -9,7 +9,17 @@
 // restart with stale fit parameters and every early exit are those of the reference; the
 // trajectory (err, Ncalls, integer minimum) is bit-identical by construction.
 #pragma once
+#ifdef UMPA_WALK_HOST
+// A host program (tests/walk_machine_check.cpp) compiles the machine itself -- Walk, walk_begin / walk_feed /
+// walk_speculate / walk_finish and the fits -- with a plain C++ compiler; the device never sees this branch.
+#include <cmath>
+#define __device__
+#define __forceinline__ inline
+static inline int __ffs(int x) { return __builtin_ffs(x); }
+using std::round;
+#else
 #include <hip/hip_runtime.h>
+#endif
 
 #define UMPA_ST_OK        1
 #define UMPA_ST_BOUND     2
@@ -27,6 +37,7 @@
 
 namespace umpa {
 
+#ifndef UMPA_WALK_HOST
 // Pointers that reach a kernel inside a by-value struct, or are loaded from a descriptor table, are
 // "generic" to the compiler and turn into flat_load / flat_store, which also tick the LDS counter
 // (lgkmcnt) and so serialise against ds_read / ds_write.  Every such pointer is device memory here:
@@ -46,6 +57,7 @@ __device__ __forceinline__ double fast_rcp(double x)
     r = fma(fma(-x, r, 1.0), r, r);
     return r;
 }
+#endif
 
 struct Fit { double t, v; };       // the CostArgs payload (Model.h:29-52)
 
@@ -68,13 +80,12 @@ struct LdsMemo {
 
 struct Walk {
     int ci, cj;        // integer centre of the 5x5 neighbourhood
-    int req_i, req_j;  // shift whose cost is wanted next
+    int req_i, req_j;  // shift whose cost is wanted next: always a cell of the neighbourhood, (req_i - ci + 2, req_j - cj + 2)
     int axis;          // 0: columns (west/east), 1: rows
-    int found0, found1;
+    int found;         // bit a: a minimum along axis a was found at this centre (the reference's found[a] != 0)
     int n;             // cost calls so far (minimizer_debug::Ncalls)
     int phase;
-    int g;             // gather: the cell 0..15 being asked for
-    unsigned need;     // gather: cells of the 4x4 neighbourhood still unknown (bit g)
+    unsigned need;     // gather: cells of the 4x4 neighbourhood still unknown (bit g); the lowest one is being asked for
     int ip, jp;        // quadrant of the 4x4 neighbourhood
     double c0;         // cost at the centre
     int status;
@@ -84,7 +95,8 @@ struct Walk {
     int bi, bj;        // (ci - 2) mod 5, (cj - 2) mod 5: torus row / column of cell (0,0)
 };
 
-__device__ __forceinline__ int wrap5(int x) { return x >= 5 ? x - 5 : x; }                  // x in [0, 9]
+// x in [0, 9]; as unsigned numbers x - 5 wraps far above x where x < 5, so the smaller of the two is x mod 5
+__device__ __forceinline__ int wrap5(int x) { const unsigned u = (unsigned)x, v = u - 5u; return (int)(u < v ? u : v); }
 __device__ __forceinline__ int mod5(int x) { const int r = x % 5; return r < 0 ? r + 5 : r; }
 // LDS slot of cell (r, c), 0 <= r, c <= 4
 __device__ __forceinline__ int walk_slot(const Walk& w, int r, int c) { return 5 * wrap5(w.bi + r) + wrap5(w.bj + c); }
@@ -195,10 +207,9 @@ __device__ inline void walk_begin(Walk& w, Memo memo, double u0, double u1)
     w.req_i = w.ci;
     w.req_j = w.cj;
     w.axis = 0;
-    w.found0 = w.found1 = 0;
+    w.found = 0;
     w.n = 0;
     w.phase = PH_CENTRE;
-    w.g = 0;
     w.need = 0;
     w.ip = w.jp = 0;
     w.c0 = 0.0;
@@ -220,137 +231,141 @@ __device__ inline void walk_begin(Walk& w, Memo memo, double u0, double u1)
 // "memoised" (:300,331) comparisons are the same expression on the same numbers, so only the
 // snapshot `args_copy = *args` (:296,327) depends on which one it was.  The centre value rides in a
 // register (`c0`): after a move it is the neighbour that was just compared.
+//
+// How it is written decides what it compiles to.  Every lane of a wave is somewhere else in its walk, so the wave runs
+// the union of all paths in any case; what costs is what the compiler adds where paths part and meet.  With an early
+// `return` per outcome and a `continue` in the scan loop, every exit carried its own version of the whole state to the
+// loop's one structurised exit: half of the function's vector instructions were register copies.  Here
+//   * there is one way out: the outcomes are predicates, and each changes the fields it owns in place, under an `if`
+//     without an else that nothing jumps out of -- a join of "changed" and "unchanged" needs no copy;
+//   * the delivery is the same few instructions for all four phases: the cell that was asked for follows from the
+//     request and the centre, the tie threshold from the phase;
+//   * the scan loop has one back edge, taken by the lanes that flipped the axis or stepped onto a memoised cell.
 template <class Memo>
 __device__ inline void walk_feed(Walk& w, Memo memo, int st, double val, Fit fit, int call_cap = UMPA_CALL_CAP)
 {
     w.n++;                                                      // Ncalls counts failed calls too (Optim.cpp:263-264)
-    if (!(st & UMPA_ST_OK)) {                                   // any failed call returns at once, outputs as they stand
+    const bool ok = st & UMPA_ST_OK;
+    const int ph = w.phase;
+    if (!ok) {                                                  // any failed call ends the walk at once, outputs as they stand
         w.status = st;
         w.phase = PH_DONE;
-        return;
     }
-    w.live = fit;
+    const bool centre = ph == PH_CENTRE, gat = ph == PH_GATHER;
+    // The cell asked for: (2,2) at the start, a neighbour of the centre along the axis (Optim.cpp:287-297, :320-328),
+    // or cell `g` of the 4x4 neighbourhood (:353-378).  A failed call's value goes into its slot too; the mask says
+    // that nothing is there.
+    const int r = w.req_i - w.ci + 2, c = w.req_j - w.cj + 2;
+    memo[walk_slot(w, r, c)] = val;
+    const bool restart = ok && gat && val < w.c0;               // missed a lower value: hard restart, centred there
+    const bool keep = ok && !gat && (centre || !(val > w.c0 + (ph == PH_LO ? UMPA_TIE : -UMPA_TIE)));
+    if (keep) w.kept = fit;
+    if (ok) {
+        w.live.t = restart ? w.kept.t : fit.t;                  // stale on purpose (Optim.cpp:373); field by field: a choice
+        w.live.v = restart ? w.kept.v : fit.v;                  // between two structs is a choice of addresses, and `w` goes to scratch
+        w.known = restart ? 1u << 12 : w.known | 1u << (5 * r + c);   // a restart keeps the new centre (its value sits in its slot already)
+    }
+    if (restart || (ok && centre)) w.c0 = val;
+    if (restart) {
+        w.ci = w.req_i;
+        w.cj = w.req_j;
+        int x = w.bi + r - 2, y = w.bj + c - 2;                 // in [-2, 6]
+        x += x < 0 ? 5 : 0; y += y < 0 ? 5 : 0;
+        w.bi = wrap5(x); w.bj = wrap5(y);
+        w.found = 0;
+    }
+    bool fill = ok && gat && !restart;                          // on to the next cell of the gather
+    if (fill) w.need &= w.need - 1;
+
     // The call cap is tested in one place only, the `while (Ncalls < MAX_CALLS)` header (Optim.cpp:267): after the
     // centre evaluation and after every move.  A probe of the low or the high neighbour that reaches the cap still
     // finishes its iteration (the other probe, then the move or the gather); `goto start` skips the test as well.
-    bool cap_test = w.phase == PH_CENTRE;
-    bool scan = false;
+    bool cap_test = centre;
+    bool scan = ok && !fill;
     int moves = 0;                                              // centre moves since the last cost call (UMPA_MOVE_CAP)
-    if (w.phase == PH_GATHER) {                                 // Optim.cpp:353-378
-        const int rr = w.ip + (w.g >> 2), cc = w.jp + (w.g & 3);   // the `a` entry is this cell of the neighbourhood
-        memo[walk_slot(w, rr, cc)] = val;
-        if (val < w.c0) {                                       // missed a lower value: hard restart, centred there
-            const int di = rr - 2, dj = cc - 2;
-            w.ci += di;
-            w.cj += dj;
-            int x = w.bi + di, y = w.bj + dj;                   // in [-2, 6]
-            x += x < 0 ? 5 : 0; y += y < 0 ? 5 : 0;
-            w.bi = wrap5(x); w.bj = wrap5(y);
-            w.known = 1u << 12;                                 // only the new centre (its value sits in its slot already)
-            w.c0 = val;
-            w.live = w.kept;                                    // stale on purpose (Optim.cpp:373)
-            w.found0 = w.found1 = 0;
-        } else {
-            w.known |= 1u << (5 * rr + cc);
-            w.need &= w.need - 1;
-            scan = true;
-        }
-    } else {
-        bool keep;
-        int r, c;
-        if (w.phase == PH_CENTRE) {                             // Optim.cpp:262-265
-            r = 2; c = 2;
-            w.c0 = val;
-            keep = true;
-        } else if (w.phase == PH_LO) {                          // Optim.cpp:287-297
-            r = w.axis ? 1 : 2; c = w.axis ? 2 : 1;
-            keep = !(val > w.c0 + UMPA_TIE);
-        } else {                                                // PH_HI, Optim.cpp:320-328
-            r = w.axis ? 3 : 2; c = w.axis ? 2 : 3;
-            keep = !(val > w.c0 - UMPA_TIE);
-        }
-        memo[walk_slot(w, r, c)] = val;
-        w.known |= 1u << (5 * r + c);
-        if (keep) w.kept = w.live;
-    }
-
-    while (!scan) {
-        if (cap_test && w.n >= call_cap) {
+    while (scan) {
+        const bool capped = cap_test && w.n >= call_cap;
+        cap_test = true;
+        const int ax = w.axis;
+        const bool lo_k = w.known & (ax ? 1u << 7 : 1u << 11), hi_k = w.known & (ax ? 1u << 17 : 1u << 13);
+        const bool cmp = !capped && lo_k && hi_k;
+        if (capped) {
             w.status = st & ~UMPA_ST_OK;                        // Optim.cpp:477
             w.phase = PH_DONE;
-            return;
         }
-        cap_test = true;
-        const int lr = w.axis ? 1 : 2, lc = w.axis ? 2 : 1, hr = w.axis ? 3 : 2, hc = w.axis ? 2 : 3;
-        if (!((w.known >> (5 * lr + lc)) & 1u)) {
-            w.phase = PH_LO;
-            w.req_i = w.ci - (w.axis ? 1 : 0);
-            w.req_j = w.cj - (w.axis ? 0 : 1);
-            return;
+        if (!capped && !(lo_k && hi_k)) {                       // ask for the low neighbour, or else the high one
+            const int s = lo_k ? 1 : -1;
+            w.phase = lo_k ? PH_HI : PH_LO;
+            w.req_i = w.ci + (ax ? s : 0);
+            w.req_j = w.cj + (ax ? 0 : s);
         }
-        if (!((w.known >> (5 * hr + hc)) & 1u)) {
-            w.phase = PH_HI;
-            w.req_i = w.ci + (w.axis ? 1 : 0);
-            w.req_j = w.cj + (w.axis ? 0 : 1);
-            return;
-        }
-        const double dlo = memo[walk_slot(w, lr, lc)], dhi = memo[walk_slot(w, hr, hc)];
-        const bool lo_up = dlo > w.c0 + UMPA_TIE;               // Optim.cpp:294,300
-        const bool hi_up = dhi > w.c0 - UMPA_TIE;               // Optim.cpp:325,331
-        if (lo_up && hi_up) {                                   // Optim.cpp:334-417
-            const int f = dlo < dhi ? -1 : 1;
-            if (w.axis) w.found1 = f; else w.found0 = f;
-            const int other = w.axis ? w.found0 : w.found1;
-            if (!other) {
-                w.axis ^= 1;
-                continue;
+        bool again = false;
+        if (cmp) {
+            // torus coordinates along the axis (a) and across it (b): the neighbours sit at a+1 and a+3 of line b+2
+            const int a = ax ? w.bi : w.bj, b = ax ? w.bj : w.bi, ka = ax ? 5 : 1, kb = ax ? 1 : 5;
+            const int mid = kb * wrap5(b + 2);
+            const double dlo = memo[ka * wrap5(a + 1) + mid], dhi = memo[ka * wrap5(a + 3) + mid];
+            const bool lo_up = dlo > w.c0 + UMPA_TIE;           // Optim.cpp:294,300
+            const bool hi_up = dhi > w.c0 - UMPA_TIE;           // Optim.cpp:325,331
+            const bool minimum = lo_up && hi_up;                // Optim.cpp:334-417
+            if (minimum) w.found |= 1 << ax;
+            const bool both = minimum && w.found == 3;
+            if (minimum && !both) {
+                w.axis = ax ^ 1;
+                again = true;
             }
-            // both axes have a minimum here, so the four neighbours of the centre are known
-            w.ip = memo[walk_slot(w, 3, 2)] < memo[walk_slot(w, 1, 2)] ? 1 : 0;     // Optim.cpp:344-345
-            w.jp = memo[walk_slot(w, 2, 3)] < memo[walk_slot(w, 2, 1)] ? 1 : 0;
-            // which cells of the 4x4 neighbourhood are still unknown: rows ip .. ip+3, columns jp .. jp+3 of the mask
-            const unsigned sub = w.known >> (5 * w.ip + w.jp);
-            const unsigned have = (sub & 0xFu) | ((sub >> 5) & 0xFu) << 4 | ((sub >> 10) & 0xFu) << 8 | ((sub >> 15) & 0xFu) << 12;
-            w.need = ~have & 0xFFFFu;
-            scan = true;
-        } else {                                                // Optim.cpp:420-474
-            w.uv0 = w.ci;
-            w.uv1 = w.cj;
-            w.out = w.c0;
-            bool up = lo_up;
-            if (!hi_up && !lo_up) up = dhi < dlo;
-            const int dir = up ? 1 : -1;
-            // the centre moves by `dir` along `axis` (Optim.cpp:436-470): cells that scroll in are unknown
-            if (w.axis) {
-                w.ci += dir;
-                w.bi = up ? wrap5(w.bi + 1) : (w.bi == 0 ? 4 : w.bi - 1);
-                w.known = up ? (w.known >> 5) : ((w.known << 5) & 0x1FFFFFFu);
-                w.found0 = 0;
-            } else {
-                w.cj += dir;
-                w.bj = up ? wrap5(w.bj + 1) : (w.bj == 0 ? 4 : w.bj - 1);
-                w.known = up ? ((w.known & ~0x0108421u) >> 1) : ((w.known & ~0x1084210u) << 1);
-                w.found1 = 0;
+            if (both) {
+                // both axes have a minimum here, so the four neighbours of the centre are known: the pair along the
+                // axis is in hand, the pair across it sits at b+1 and b+3 of line a+2
+                const int mida = ka * wrap5(a + 2);
+                const bool qa = dhi < dlo, qb = memo[kb * wrap5(b + 3) + mida] < memo[kb * wrap5(b + 1) + mida];
+                w.ip = (ax ? qa : qb) ? 1 : 0;                  // Optim.cpp:344-345
+                w.jp = (ax ? qb : qa) ? 1 : 0;
+                // which cells of the 4x4 neighbourhood are still unknown: rows ip .. ip+3, columns jp .. jp+3 of the mask
+                const unsigned sub = w.known >> (5 * w.ip + w.jp);
+                const unsigned have = (sub & 0xFu) | ((sub >> 5) & 0xFu) << 4 | ((sub >> 10) & 0xFu) << 8 | ((sub >> 15) & 0xFu) << 12;
+                w.need = ~have & 0xFFFFu;
+                fill = true;
             }
-            w.c0 = up ? dhi : dlo;                              // the new centre is the neighbour stepped onto
-            if (++moves > UMPA_MOVE_CAP) {                      // (never on finite costs; see UMPA_MOVE_CAP)
-                w.status = st & ~UMPA_ST_OK;
-                w.phase = PH_DONE;
-                return;
+            if (!minimum) {                                     // Optim.cpp:420-474
+                w.uv0 = w.ci;
+                w.uv1 = w.cj;
+                w.out = w.c0;
+                bool up = lo_up;
+                if (!hi_up && !lo_up) up = dhi < dlo;
+                const int dir = up ? 1 : -1;
+                // the centre moves by `dir` along `axis` (Optim.cpp:436-470): cells that scroll in are unknown
+                const int t = up ? wrap5(a + 1) : (a == 0 ? 4 : a - 1);
+                const unsigned rows = up ? (w.known >> 5) : ((w.known << 5) & 0x1FFFFFFu);
+                const unsigned cols = up ? ((w.known & ~0x0108421u) >> 1) : ((w.known & ~0x1084210u) << 1);
+                w.ci += ax ? dir : 0;
+                w.cj += ax ? 0 : dir;
+                w.bi = ax ? t : w.bi;
+                w.bj = ax ? w.bj : t;
+                w.known = ax ? rows : cols;
+                w.found &= 1 << ax;                             // the other axis has to be looked at again
+                w.c0 = up ? dhi : dlo;                          // the new centre is the neighbour stepped onto
+                again = ++moves <= UMPA_MOVE_CAP;               // (never beyond on finite costs; see UMPA_MOVE_CAP)
+                if (!again) {
+                    w.status = st & ~UMPA_ST_OK;
+                    w.phase = PH_DONE;
+                }
             }
         }
+        scan = again;
     }
     // fill the 4x4 neighbourhood, asking for what is missing in the reference's order (Optim.cpp:353-362)
-    if (w.need) {
-        w.g = __ffs(w.need) - 1;
-        w.phase = PH_GATHER;
-        w.req_i = w.ci + w.ip + (w.g >> 2) - 2;
-        w.req_j = w.cj + w.jp + (w.g & 3) - 2;
-        return;
+    if (fill) {
+        const int g = __ffs(w.need) - 1;                        // (-1 where nothing is missing: unused then)
+        w.phase = w.need ? PH_GATHER : PH_FIT;
+        if (w.need) {
+            w.req_i = w.ci + w.ip + (g >> 2) - 2;
+            w.req_j = w.cj + w.jp + (g & 3) - 2;
+        } else {
+            w.live = w.kept;                                    // Optim.cpp:386
+            w.status = st;
+        }
     }
-    w.live = w.kept;                                            // Optim.cpp:386
-    w.status = st;
-    w.phase = PH_FIT;
 }
 
 // The request that will follow the pending one -- where that is known before the pending one's cost is (the high neighbour
