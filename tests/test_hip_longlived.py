@@ -16,6 +16,11 @@ same environment, and the two results must be equal bit for bit, ``last_path`` i
 Every consumer of a live model is a step: ``match()`` (walk and grid search), ``cost_volume()``, ``smooth.match_smooth(model)``
 and ``model.uncertainty(result)``.  Trajectories 9 to 13 put the later three behind staged, updated and rewritten stacks: a
 staged stack is adopted by the FIRST call that reads the sample stack, whichever it is, and the last stack given wins.
+The table's later consumers are steps of the harness too -- ``basins()``, ``track()``, ``sequence()``, ``widen=b`` on the grid
+search, the volume, ``basins`` and ``track``, ``widen.coarse_to_fine``, ``levels.scale_space``, ``uncertainty(resident=True)`` --
+and the ``masked_grid`` switch is a mutation of the record; their trajectories, and those of ``Tracker`` and ``Sequence``, are
+in ``test_hip_longlived_consumers.py``.  Where such a call takes HIP tensors (priors, states, ``out=``) the live model is given
+tensors, the twin the same numbers as host arrays, and the downloaded maps are compared.
 
 Each trajectory prints one line (steps compared, paths seen) for the record.
 """
@@ -40,6 +45,34 @@ def hip_ns():
 
 def _copy(res):
     return {k: np.array(v) for k, v in res.items() if isinstance(v, np.ndarray)}
+
+
+def _download(res, prefix=""):
+    """_copy for the table consumers' results: HIP tensors are downloaded, and `region` -- two (start, end, step) triples -- is
+    kept as an int array, so that it is compared like a map"""
+    out = {}
+    for k, v in res.items():
+        if k == "region":
+            out[prefix + k] = np.array(v, dtype=np.int64)
+        elif hasattr(v, "data_ptr"):
+            out[prefix + k] = v.cpu().numpy()
+        elif isinstance(v, np.ndarray):
+            out[prefix + k] = np.array(v)
+    return out
+
+
+def _levels(pair):
+    """(result, all) of coarse_to_fine / scale_space as one dictionary: `sel.<key>` and `L<n>.<key>`"""
+    sel, every = pair
+    out = _download(sel, "sel.")
+    for n, r in enumerate(every):
+        out.update(_download(r, "L%d." % n))
+    return out
+
+
+def _to_device(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def _device_frames(a):
@@ -74,13 +107,15 @@ class LongLived:
         self.ns, self.label, self.borrowed = hip_ns, label or cls, borrowed
         self.rec = dict(cls=cls, sam=("host", np.ascontiguousarray(sam)), ref=np.ascontiguousarray(ref), mask=mask, pos=pos,
                         window_size=window_size, max_shift=max_shift, Nw=None, assign="sam", subpx=-1, debug=True, ROI=None,
-                        force=force, unwarp=None)
+                        force=force, unwarp=None, masked_grid=False)
+        self.adopted = self.rec["sam"]                                # the stack the library matches: a staged one is not, yet
         self.live = self._construct()
         self.steps, self.paths = 0, []
 
     # -- a model that has only ever been in the recorded state
-    def _construct(self):
-        r = self.rec
+    def _construct(self, sam=None):
+        """sam: this sample-stack entry in place of the record's (the stack last adopted, while another is staged)"""
+        r = self.rec if sam is None else dict(self.rec, sam=sam)
         kw = dict(window_size=r["window_size"], max_shift=r["max_shift"])
         if r["mask"] is not None:
             kw["mask_list"] = r["mask"]
@@ -99,6 +134,8 @@ class LongLived:
         m.debug = r["debug"]
         if r["ROI"] is not None:
             m.ROI = r["ROI"]
+        if r["masked_grid"]:
+            m.masked_grid = True
         if kind == "staged":
             raw, dark, flat = payload
             if r["unwarp"] is not None:
@@ -113,10 +150,16 @@ class LongLived:
             setattr(self.live, names[k], v)
             self.rec[k] = v
 
+    def set_masked(self, on):
+        """the masked_grid switch of a model with masks"""
+        self.live.masked_grid = on
+        assert self.live.masked_grid is bool(on)
+        self.rec["masked_grid"] = bool(on)
+
     def update(self, sam=None, ref=None):
         self.live.update_frames(sam_list=sam, ref_list=ref)
         if sam is not None:
-            self.rec["sam"] = ("host", np.ascontiguousarray(sam))
+            self.rec["sam"] = self.adopted = ("host", np.ascontiguousarray(sam))
         if ref is not None:
             self.rec["ref"] = np.ascontiguousarray(ref)
 
@@ -145,9 +188,13 @@ class LongLived:
     def _path(self, m):
         return m._lib.last_path(m._handle)
 
-    def _check(self, got, path, roi, call, what, expect_path=None, need=None):
-        """got, path, roi: the live model's maps, last_path and ROI after its call; `call(twin)` makes the same call"""
-        twin = self._construct()
+    def _check(self, got, path, roi, call, what, expect_path=None, need=None, pending=False):
+        """got, path, roi: the live model's maps, last_path and ROI after its call; `call(twin)` makes the same call.
+        pending: the live call read the sample stack without adopting a staged one, and so does the twin's: it is built from
+        the stack adopted last"""
+        twin = self._construct(self.adopted if pending else None)
+        if not pending:
+            self.adopted = self.rec["sam"]
         want = _copy(call(twin))
         self.steps += 1
         self.paths.append(path)
@@ -209,6 +256,95 @@ class LongLived:
         twin_kw = given if self.rec["sam"][0] == "staged" else {}
         return self._check(got, self._path(self.live), self.live.ROI, lambda m: call(m, twin_kw),
                            what or "uncertainty %r %r" % (result_kw if smooth_kw is None else smooth_kw, kw), need=("unit", "s2", "dof", "valid"))
+
+    # -- the table's other consumers: basins, track, sequence, widening, the level chains, the resident uncertainty maps.
+    #    Every call states lam, trunc and radius itself; with device=True the live model is given HIP tensors and its maps are
+    #    downloaded, the twin is given the same numbers as host arrays.
+    def _fit(self):
+        return ("f", "T", "dx", "dy", "err") + (("df",) if self.rec["cls"] == "UMPAModelDF" else ())
+
+    def _extra(self, kw):
+        """`region` of a widened call; `covered` of a masked model with the switch on"""
+        return (("region",) if kw.get("widen") else ()) + (("covered",) if self.rec["masked_grid"] else ())
+
+    def grid(self, what="", expect_path=None, **kw):
+        """match(search='grid', **kw), `region` of a widened call included"""
+        got = _download(self.live.match(quiet=True, search="grid", **kw))
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: _download(m.match(quiet=True, search="grid", **kw)),
+                           what or "grid %r" % (kw,), expect_path, need=self._maps() + (("region",) if kw.get("widen") else ()))
+
+    def volume(self, what="", **kw):
+        """cost_volume(**kw), `region` and `covered` included"""
+        got = _download(self.live.cost_volume(**kw))
+        fit = ("T",) + (("df",) if self.rec["cls"] == "UMPAModelDF" else ()) if kw.get("with_fit") else ()
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: _download(m.cost_volume(**kw)),
+                           what or "cost_volume %r" % (kw,), need=("cost",) + fit + self._extra(kw))
+
+    def basins(self, what="", **kw):
+        assert "k" in kw
+        got = _download(self.live.basins(**kw))
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: _download(m.basins(**kw)),
+                           what or "basins %r" % (kw,), need=self._fit() + ("cost", "shift", "count") + self._extra(kw))
+
+    def track(self, prior_dx, prior_dy, what="", device=False, **kw):
+        assert "lam" in kw and "radius" in kw
+        given = [_to_device(p) if device and isinstance(p, np.ndarray) else p for p in (prior_dx, prior_dy)]
+        res = self.live.track(given[0], given[1], **kw)
+        assert hasattr(res["dx"], "data_ptr") == (device and any(isinstance(p, np.ndarray) for p in (prior_dx, prior_dy)))
+        return self._check(_download(res), self._path(self.live), self.live.ROI, lambda m: _download(m.track(prior_dx, prior_dy, **kw)),
+                           what or "track %r" % (kw,), need=self._fit() + ("cost", "cost0", "shift", "count", "found") + self._extra(kw))
+
+    def sequence(self, what="", state=None, device=False, **kw):
+        """state: a host array, or None where a series starts; the twin gets exactly it.  device=True: the live model reads a
+        HIP copy of it and writes the next state into a tensor given as out="""
+        assert "lam" in kw and "trunc" in kw
+        if device:
+            import torch
+            _, _, N0, N1 = self.live._region(kw.get("ROI"), kw.get("step"), ROI_wins=True)
+            U = 2 * self.rec["max_shift"] - 1
+            out = torch.empty((U, U, N0, N1), dtype=torch.float64, device="cuda:0")
+            res = self.live.sequence(state=None if state is None else _to_device(state), out=out, **kw)
+            assert res["state"].data_ptr() == out.data_ptr() and res["dx"].is_cuda
+        else:
+            res = self.live.sequence(state=state, **kw)
+        keys = self._fit() + ("state", "cost", "total", "cost0", "shift", "moved") + self._extra(kw)
+        return self._check(_download(res), self._path(self.live), self.live.ROI, lambda m: _download(m.sequence(state=state, **kw)),
+                           what or "sequence %r" % (kw,), need=keys)
+
+    def coarse_to_fine(self, what="", **kw):
+        """widen.coarse_to_fine(model, **kw) over the remembered ROI: every level's maps and regions"""
+        from umpa_amd import widen
+        assert "levels" in kw and "lam" in kw and "radius" in kw
+        got = _levels(widen.coarse_to_fine(self.live, **kw))
+        keys = tuple("%s.%s" % (p, k) for p in ["sel"] + ["L%d" % n for n in range(len(kw["levels"]))] for k in ("dx", "dy", "err", "region"))
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: _levels(widen.coarse_to_fine(m, **kw)),
+                           what or "coarse_to_fine %r" % (kw,), need=keys)
+
+    def scale_space(self, what="", **kw):
+        """levels.scale_space(model, **kw): the selected maps, `level` and `halfwidth`, and every level's maps and regions"""
+        from umpa_amd import levels
+        assert "levels" in kw and "tol" in kw and "lam" in kw and "radius" in kw
+        got = _levels(levels.scale_space(self.live, **kw))
+        keys = tuple("%s.%s" % (p, k) for p in ["sel"] + ["L%d" % n for n in range(len(kw["levels"]))] for k in ("dx", "dy", "err", "found", "region"))
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: _levels(levels.scale_space(m, **kw)),
+                           what or "scale_space %r" % (kw,), need=keys + ("sel.level", "sel.halfwidth"))
+
+    def resident(self, result_kw, what="", result=None, pending=False, **kw):
+        """model.uncertainty(res, resident=True, **kw) with res = model.match(**result_kw): unit, s2, dof, valid.  The twin is
+        always one that adopted the same stack by the same route -- built on it, or staged through the kernel and adopted by
+        its own match(**result_kw).  result: the maps of an earlier step with result_kw, and then the live model makes no
+        match here: it reads the buffer as the calls before left it.  pending: a stack is staged and not adopted, the live
+        call reads the one adopted before it, and the twin is a model of THAT stack (result is then required)."""
+        assert not pending or result is not None
+
+        def call(m, res):
+            res = m.match(quiet=True, **result_kw) if res is None else res
+            u = m.uncertainty(res, resident=True, **({} if res is not result else {"ROI": result_kw.get("ROI")}), **kw)
+            return {"unit": u.unit, "s2": u.s2, "dof": u.dof, "valid": u.valid}
+
+        got = _copy(call(self.live, result))
+        return self._check(got, self._path(self.live), self.live.ROI, lambda m: call(m, None), what or "uncertainty(resident=True) %r %r" % (result_kw, kw),
+                           need=("unit", "s2", "dof", "valid"), pending=pending)
 
     def report(self):
         print("\n[long-lived] %s: %d match steps compared, last_path values %s" % (self.label, self.steps, sorted(set(self.paths))))
