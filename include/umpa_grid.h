@@ -60,6 +60,34 @@ extern "C" {
  * in the windowed sums, so a box average of costs is not the cost under a wider window. */
 int umpa_grid_set_masked(umpa_hip_model *m, int on);
 
+/* The general table: the per-model switch for everything no tiled path takes whole, off by default.  A NULL model is
+ * UMPA_HIP_E_ARG; the state lives with the model and dies with it.  `on`: 0 off; 1 on; 3 on, and also for a model and region
+ * a tiled path would take (the caller wants the explicit sum everywhere, as a model forced onto the direct kernel does).
+ *
+ * With the switch off every function below refuses what it refused before, with the same text.  With it on,
+ * umpa_grid_match_region, _cost_volume, _basins, _track, _sequence and the umpa_grid_wide_ four with b = 0 also take: frames at
+ * different positions (sample stepping) or of unequal shapes, a model forced onto the direct kernel
+ * (UMPA_HIP_F_FORCE_DIRECT), a model with masks whose umpa_grid_set_masked switch is off or that the masked tiled path does
+ * not admit, steps and search ranges past the tiled limits -- everything the general kernels of umpa_hip_match_region
+ * take, except the kernel dark-field model, which has no per-shift table.  Whatever a tiled path takes whole keeps going
+ * there (on = 1): its numbers do not change with the switch.
+ * The general table holds, for every requested pixel and every integer shift of the search box, the FINISHED cost,
+ * transmission and dark-field value of the model: the reference's own window x frame sum (frames outer, window rows, then
+ * columns; a frame contributes to a pixel iff the pixel keeps `padding` from its edges; the cost is divided by the frame
+ * count without masks and by the sum of the pair weights with them), equal bit for bit to umpa_hip_cost of the same pixel
+ * and shift.  It is filled per row chunk within the table budget of the tiled paths (UMPA_HIP_TABLE_MB), on the requested
+ * pixels only, whatever the steps.  Every rule stated below then holds word for word with C[s] that cost, as on a masked
+ * model (umpa_grid_set_masked): argument checks, their order and texts, flags, the staged stack, device I/O; the result maps of
+ * umpa_grid_match_region are downloaded in one piece.
+ * Coverage.  umpa_grid_match_region takes `covermap` / `cover_threshold` and skips the pixels below the threshold; the other
+ * functions compute EVERY pixel of the region.  A pixel no frame contributes to (and, with masks, a window without any pair
+ * weight) has NaN costs, and the NaN rules below give the "no finite cost" result.
+ * Window widening (b > 0) and umpa_grid_levels_track on a model and region that go this way are UMPA_HIP_E_UNSUPPORTED: a
+ * finished cost is not linear in the windowed sums, so a box average of costs is not the cost under a wider window.
+ * The arithmetic per pixel is 3 * frames * window pixels FMAs for EVERY shift: about 38 times the plain tiled path's at ten
+ * frames, an 11 x 11 window and 81 shifts. */
+int umpa_grid_set_general(umpa_hip_model *m, int on);
+
 /* The arguments, flags (UMPA_HIP_F_DEVICE_IO, _PLANAR, _REUSE_REF_MAPS, _USE_STAGED, _ASYNC), chunked downloads and the
  * rows callback of umpa_hip_match_region.  `uv` must be NULL (start shifts mean nothing to an exhaustive search:
  * UMPA_HIP_E_ARG).  Per pixel:

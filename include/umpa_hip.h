@@ -199,7 +199,8 @@ int umpa_hip_timing_read(umpa_hip_model *m, int index, const char **name, double
  * geometry; filled in for corr_volume, 0 for kernels that do not report it): the numerator of roofline.fp64_fma */
 int umpa_hip_timing_fma(umpa_hip_model *m, int index, double *fma);
 /* which path the last match_region took: 0 none, 1 direct (plain), 2 tiled, 3 direct (staged: windows out of LDS),
- * 4 sample stepping: tiled on the rectangle every frame contributes to + general kernels on the border strips */
+ * 4 sample stepping: tiled on the rectangle every frame contributes to + general kernels on the border strips,
+ * 5 the grid library's kernels on a table of finished costs of their own (include/umpa_grid.h: umpa_grid_set_general) */
 int umpa_hip_last_path(umpa_hip_model *m);
 /* the tiled path can compute only the passes of its shift table that walks read (seed tiles predict, misses are repaired:
  * the maps are those of the exhaustive table; never where corr_march computes the table: there units computed == units

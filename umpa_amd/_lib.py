@@ -180,6 +180,8 @@ GRID_SEQUENCE_MIN_MS, GRID_SEQUENCE_MAX_MS = 2, 8                # the search ra
 _GRID_ABI["sequence"] = (_int, [_vp] + [_int] * 6 + [_vp, _dbl, _dbl, _vp] + [_vp] * 12 + [_int, _vp])
 # umpa_grid_set_masked: the model, on / off (the per-model switch that admits a masked model to the calls above)
 _GRID_ABI["set_masked"] = (_int, [_vp, _int])
+# umpa_grid_set_general: the model, 0 / 1 / 3 (the per-model switch of the general table: what no tiled path takes whole)
+_GRID_ABI["set_general"] = (_int, [_vp, _int])
 # umpa_grid_uncertainty: the model and the region, shift, moments (or NULL), unit, s2, dof, valid
 GRID_SIGMA_PLANES = (17, 50)                                     # UMPA_GRID_SIGMA_PLANES_PLAIN, _DF: a model with masks
 _GRID_ABI["uncertainty"] = (_int, [_vp] + [_int] * 6 + [_vp] * 6 + [_int, _vp])

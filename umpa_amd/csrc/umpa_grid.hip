@@ -2,8 +2,8 @@
 //
 // A second library, built from the headers of libumpa_hip.so by the same build: it holds the kernel families of
 // umpa_grid_kernels.h, umpa_basins_kernels.h, umpa_track_kernels.h, umpa_widen_kernels.h, umpa_levels_kernels.h and
-// umpa_sequence_kernels.h, their twins on a masked model's table of finished costs (umpa_masked_grid_kernels.h) and no other
-// feature code.  A call sets itself as the model's table
+// umpa_sequence_kernels.h, their twins on a masked model's table of finished costs (umpa_masked_grid_kernels.h), the kernel
+// that fills such a table for the models no tiled path takes (umpa_general_table_kernels.h) and no other feature code.  A call sets itself as the model's table
 // consumer (umpa_hipx.h), runs umpa_hip_match_region down the tiled path -- whose argument checks, uploads, row chunks, downloads and callbacks are
 // therefore the existing ones -- and clears the consumer again.  No CPU fallback.
 // One call is no table consumer: umpa_grid_uncertainty (umpa_resident_kernels.h, at the end of this file) runs one kernel on the
@@ -22,6 +22,7 @@
 #include "umpa_levels_kernels.h"
 #include "umpa_sequence_kernels.h"
 #include "umpa_masked_grid_kernels.h"
+#include "umpa_general_table_kernels.h"
 #include "umpa_resident_kernels.h"
 
 using namespace umpa;
@@ -93,6 +94,10 @@ struct GridJob {
     // an admitted masked model (umpa_grid_set_masked): the planes per shift of its table of finished costs, 2 or 3
     // (umpa_hipx_masked_table); 0: the plain path's table.  The kernels are then those of umpa_masked_grid_kernels.h.
     int masked = 0;
+    // the general table (umpa_grid_set_general): one table of finished costs for the call's row chunks, from the stream-ordered
+    // allocator on the call's stream, given back on it when the call has enqueued its last kernel
+    void* gtable = nullptr;
+    hipStream_t gstream = nullptr;
 };
 
 // the block of umpa_grid_wide_match_region's host path: values, dbg_d, dbg_a, cover (doubles), then err, dbg_n (ints)
@@ -524,6 +529,65 @@ hipError_t consumer(void* user, const ModelDev& dev, const Maps& M0, const Repla
     return dispatch(J, dev, M, R, A, s);
 }
 
+const char* const FINISHED_COST = "a finished cost is not linear in the windowed sums, so a box average of costs is not the cost under a wider window";
+
+template <int KIND, bool MASK>
+void launch_general(const ModelDev& dev, const RegionArgs& A, const GeneralArgs& T, const StagedGeom& G, size_t lds, hipStream_t s)
+{
+    const dim3 grd((A.N1 + UMPA_STAGED_BX - 1) / UMPA_STAGED_BX, (T.rows + UMPA_STAGED_BY - 1) / UMPA_STAGED_BY);
+    hipLaunchKernelGGL((general_table_kernel<KIND, MASK>), grd, dim3(UMPA_STAGED_BX, UMPA_STAGED_BY), T.staged ? lds : 0, s, dev, A, T, G);
+}
+
+// The general consumer (umpa_hipx_set_general_consumer): the match entry point calls it once, with the full region, where a
+// table consumer is set and no tiled path takes the model and the region whole.  Per row chunk of the region -- as many
+// output rows as the tiled paths' table budget holds (UMPA_HIP_TABLE_MB) -- general_table_kernel fills a table of finished
+// costs on the OUTPUT grid (umpa_general_table_kernels.h), and the call's consumer runs on it as on the masked path's: the
+// ReplayArgs of that path, GridJob::masked = NV, and the region with unit steps (the masked kernels use the steps only to
+// find a pixel in the table).
+hipError_t general(void* user, const ModelDev& dev, int kind, int has_mask, const RegionArgs& A, hipStream_t s)
+{
+    GridJob& J = *(GridJob*)user;
+    if (J.b > 0 || J.L > 0) {
+        J.refused_text = std::string("window widening and scale space are not built for the general table (umpa_grid_set_general): it "
+                                     "holds finished costs, and ") + FINISHED_COST;
+        J.refused = J.refused_text.c_str(); J.refused_code = UMPA_HIP_E_UNSUPPORTED;
+        return hipErrorInvalidValue;
+    }
+    if (A.N0 <= 0 || A.N1 <= 0 || dev.ms < 1) return hipSuccess;
+    const int U = 2 * dev.ms - 1, NV = kind == UMPA_HIP_KIND_DF ? 3 : 2;
+    const TiledEnv E = tiled_env();
+    const size_t per_row = (size_t)U * U * NV * A.N1;                 // doubles per output row
+    long rows_chunk = (long)(E.table_bytes / (per_row * sizeof(double))) / UMPA_STAGED_BY * UMPA_STAGED_BY;
+    if (rows_chunk < UMPA_STAGED_BY) rows_chunk = UMPA_STAGED_BY;
+    if (rows_chunk > A.N0) rows_chunk = A.N0;
+    if (hipMallocAsync(&J.gtable, per_row * rows_chunk * sizeof(double), s) != hipSuccess) { J.gtable = nullptr; return hipErrorOutOfMemory; }
+    J.gstream = s;
+    J.masked = NV;
+    StagedGeom G = {};
+    size_t lds = 0;
+    const bool staged = general_geometry(dev, has_mask != 0, A, G, lds);
+    RegionArgs Au = A;                                                // the table lies on the output grid
+    Au.step0 = 1; Au.step1 = 1;
+    const Maps none = {};
+    for (int row0 = 0; row0 < A.N0; row0 += (int)rows_chunk) {
+        const int rows = std::min((int)rows_chunk, A.N0 - row0);
+        GeneralArgs T;
+        T.table = (double*)J.gtable; T.slot_stride = (size_t)rows * A.N1; T.row0 = row0; T.rows = rows; T.staged = staged ? 1 : 0;
+        if (kind == UMPA_HIP_KIND_DF) { if (has_mask) launch_general<1, true>(dev, A, T, G, lds, s); else launch_general<1, false>(dev, A, T, G, lds, s); }
+        else { if (has_mask) launch_general<0, true>(dev, A, T, G, lds, s); else launch_general<0, false>(dev, A, T, G, lds, s); }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        ReplayArgs R;
+        memset(&R, 0, sizeof(R));
+        R.table = T.table; R.slot_stride = T.slot_stride; R.drow0 = row0; R.N1d = A.N1;
+        R.strip_w = 0; R.tw = 0; R.drows = rows;
+        R.row0 = row0; R.rows = rows;
+        R.bw_log2 = 4;
+        if ((e = consumer(user, dev, none, R, Au, s)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // umpa_hip_match_region down the tiled path with `J` as the model's table consumer; the consumer is cleared whatever happens
 int run(umpa_hip_model* m, GridJob& J, int start0, int step0, int N0, int start1, int step1, int N1,
         double* values, int nparam, int* err, const double* covermap, double thr,
@@ -539,6 +603,7 @@ int run(umpa_hip_model* m, GridJob& J, int start0, int step0, int N0, int start1
                                          dbg_d, dbg_a, dbg_n, flags | UMPA_HIP_F_FORCE_TILED, stream);
     (void)umpa_hipx_set_table_consumer(m, nullptr, nullptr);
     if (J.ws) { (void)hipFreeAsync(J.ws, J.ws_stream); J.ws = nullptr; }   // (widening) behind the call's last kernel on its stream
+    if (J.gtable) { (void)hipFreeAsync(J.gtable, J.gstream); J.gtable = nullptr; }   // (the general table) likewise
     if (rc < 0) return fail(J.refused && J.refused_code ? J.refused_code : rc, "grid: %s", J.refused ? J.refused : umpa_hip_last_error());
     return rc;
 }
@@ -871,6 +936,13 @@ UMPA_GRID_API int umpa_grid_set_masked(umpa_hip_model* m, int on)
 {
     if (!m) return fail(UMPA_HIP_E_ARG, "grid: set_masked: null model");
     if (int rc = umpa_hipx_set_masked_consumer(m, on)) return fail(rc, "%s", umpa_hip_last_error());
+    return 0;
+}
+
+UMPA_GRID_API int umpa_grid_set_general(umpa_hip_model* m, int on)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "grid: set_general: null model");
+    if (int rc = umpa_hipx_set_general_consumer(m, on ? general : nullptr, (on & 2) ? 1 : 0)) return fail(rc, "%s", umpa_hip_last_error());
     return 0;
 }
 

@@ -158,6 +158,8 @@ struct umpa_hip_model {
     MapBufs t;                                     // dense maps of a sub-rectangle (sample-stepping split)
     TiledState tiled;                              // scratch of the tiled fast path
     int last_path = 0;
+    umpa_hipx_general_consumer general_fn = nullptr;                  // umpa_hipx_set_general_consumer
+    bool general_always = false;
     bool timing = false;
     std::vector<TimedLaunch> launches;
     std::vector<hipEvent_t> event_pool;
@@ -648,6 +650,28 @@ int run_match(umpa_hip_model* m, const RegionArgs& A, int flags, hipStream_t s,
     // a masked model whose switch is on (umpa_hipx_set_masked_consumer): the consumer takes the masked path's table of
     // finished costs, where that path takes the model and the region of its own accord -- UMPA_HIP_F_FORCE_TILED, which the
     // consumers set, lifts the exact-fit gate and the step limit in tiled_applicable, so both are asked again here
+    // the general consumer (umpa_hipx_set_general_consumer): what is about to be refused here goes to it instead, once, with
+    // the full region -- it fills a table of finished costs with a kernel of its own and runs the table consumer on it.  What a
+    // tiled path takes whole keeps going there (unless the switch says always).  Host code only.
+    auto general = [&]() -> int {
+        hipError_t e;
+        {
+            ScopedTimer t(m, s, KN_CONSUMER);                         // "table_consumer": the table kernel and the consumer's, all chunks
+            e = m->general_fn(m->tiled.consumer_user, m->dev(), m->kind, m->has_mask ? 1 : 0, A, s);
+        }
+        if (e == hipErrorOutOfMemory) return fail(UMPA_HIP_E_NOMEM, "general table: device scratch allocation failed");
+        if (e != hipSuccess) return fail(UMPA_HIP_E_LAUNCH, "general table: launch failed (%d): %s", (int)e, hipGetErrorString(hipGetLastError()));
+        if (on_rows) on_rows(0, A.N0);
+        m->last_path = 5;
+        return 0;
+    };
+    const bool can_general = m->tiled.consumer && m->general_fn && m->kind != UMPA_HIP_KIND_DFKERNEL;
+    const bool takes_whole = whole && (!m->has_mask || m->tiled.masked_consumer) && !(flags & UMPA_HIP_F_FORCE_DIRECT);
+    if (can_general && (m->general_always || !takes_whole)) return general();
+    if (can_general && m->has_mask && m->tiled.masked_consumer) {
+        char why[200];
+        if (masked_consumer_refusal(m, A, why, sizeof(why))) return general();
+    }
     if (m->tiled.consumer && m->has_mask && m->tiled.masked_consumer && m->kind != UMPA_HIP_KIND_DFKERNEL) {
         char why[200];
         if (masked_consumer_refusal(m, A, why, sizeof(why)))
@@ -1373,6 +1397,13 @@ int umpa_hipx_set_table_consumer(umpa_hip_model* m, umpa::TableConsumer fn, void
 {
     if (!m) return fail(UMPA_HIP_E_ARG, "null model");
     m->tiled.consumer = fn; m->tiled.consumer_user = fn ? user : nullptr;
+    return 0;
+}
+
+int umpa_hipx_set_general_consumer(umpa_hip_model* m, umpa_hipx_general_consumer fn, int always)
+{
+    if (!m) return fail(UMPA_HIP_E_ARG, "null model");
+    m->general_fn = fn; m->general_always = fn && always;
     return 0;
 }
 

@@ -38,6 +38,23 @@ int umpa_hipx_set_masked_consumer(umpa_hip_model* m, int on);
 // no masks or its switch is off, the table is the plain path's.
 int umpa_hipx_masked_table(const umpa_hip_model* m);
 
+// The general consumer of a model (include/umpa_grid.h: umpa_grid_set_general), set (fn != NULL) or cleared; it lives with the
+// model.  Where a table consumer is set and a match is about to be refused because no tiled path takes the model and the
+// region whole -- frames at different positions or of unequal shapes, forced direct, a masked model whose switch is off or
+// that the masked path does not admit, steps or search ranges past the tiled limits; never the kernel dark-field model --
+// the match calls `fn(user, dev, kind, has_mask, A, stream)` ONCE instead: `user` is the table consumer's, `dev` the
+// model's ModelDev, `kind` UMPA_HIP_KIND_*, `A` the full region as the general kernels take it (dense arrays, device
+// pointers, cover and thr as given).  `fn` fills tables of finished costs with kernels of its own and runs the table
+// consumer on them; hipSuccess, or an error the match reports (hipErrorOutOfMemory: UMPA_HIP_E_NOMEM).  Everything around
+// the call is umpa_hip_match_region's as it is: uploads, the staged stack, device I/O, planar maps, asynchronous matches,
+// the downloads (one piece: all rows), the coverage threshold.  What a tiled path takes whole keeps going there, unless
+// `always` is set (the caller wants the explicit window x frame sum everywhere, as a model forced onto the direct kernel
+// does).  With no general consumer set every call, refusal and text is what it was.  Host code only: no kernel of
+// libumpa_hip.so knows of it.
+typedef hipError_t (*umpa_hipx_general_consumer)(void* user, const umpa::ModelDev& dev, int kind, int has_mask,
+                                                 const umpa::RegionArgs& A, hipStream_t stream);
+int umpa_hipx_set_general_consumer(umpa_hip_model* m, umpa_hipx_general_consumer fn, int always);
+
 // The model as its own kernels see it (umpa_grid_uncertainty runs a kernel of libumpa_grid.so on the model's device frames):
 // `*dev` is the model's ModelDev -- the descriptor table (per frame sam, ref, mask, shape and position), the window and its
 // sum, Na, Nw, max_shift, padding, ref_mode -- `*kind` UMPA_HIP_KIND_*, `*has_mask` 0 or 1, `*device` its device, `*stream`

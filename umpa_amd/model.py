@@ -399,12 +399,30 @@ class UMPAModelBase:
         """A model with masks whose ``masked_grid`` switch is on (a stub without the attribute counts as off)."""
         return self._mask is not None and bool(getattr(self, "_masked_grid", False))
 
+    def _general_admitted(self):
+        """The ``general_grid`` switch is on (a stub without the attribute counts as off)."""
+        return bool(getattr(self, "_general_grid", False))
+
+    def _goes_general(self):
+        """With ``general_grid`` on: the model is one the tiled paths never take whole, so its grid consumers run on the general
+        table (steps and search ranges past the tiled limits go there too, but only the library knows those)."""
+        return self._general_admitted() and ((self._mask is not None and not self._masked_admitted())
+                                             or not self._one_frame_box() or bool(self._force & _lib.F_FORCE_DIRECT))
+
+    def _marks_covered(self):
+        """The consumers without a coverage argument compute every pixel and return ``covered``: an admitted masked model, or a
+        model on the general table whose coverage is not trivial."""
+        return self._masked_admitted() or (self._goes_general() and not self._trivial_coverage())
+
     def _covered(self, s0, s1):
         """``coverage >= thr`` on the region, with the threshold of ``match()`` (model.pyx:431): a numpy bool ``[N0, N1]``."""
         covermap = self.coverage(ROI=(s0, s1))
         return covermap >= .1 * covermap.max() / len(self._sam)
 
     def _no_masked_widening(self, what):
+        if self._goes_general():
+            raise RuntimeError("%s: not available on the general table (general_grid): it holds finished costs, and a finished cost is "
+                               "not linear in the windowed sums, so a box average of costs is not the cost under a wider window" % what)
         if self._masked_admitted():
             raise RuntimeError("%s: not available on a masked model: its table holds finished costs, and a finished cost is not "
                                "linear in the windowed sums, so a box average of costs is not the cost under a wider window" % what)
@@ -550,6 +568,12 @@ class UMPAModelBase:
             why = "it runs on the HIP library only"
         elif self._kind == KIND_DFKERNEL:
             why = "the kernel dark-field model has no shift table"
+        elif self._general_admitted():
+            # the general table takes masks, positions, shapes and a forced direct kernel; a forced model's consumers other
+            # than match() pass no force flag, so the library's switch carries the wish
+            if getattr(self, "_handle", None) is not None:
+                always = 2 if self._force & _lib.F_FORCE_DIRECT else 0
+                _lib.grid().check(_lib.grid().set_general(self._handle, 1 | always), "grid set_general")
         elif self._mask is not None and not self._masked_admitted():
             why = "masked models are not supported (their table holds finished costs)"
         elif not self._one_frame_box():
@@ -593,7 +617,7 @@ class UMPAModelBase:
         s0, s1, out = self._grid_cost_volume(ROI, step, lambda U, N0, N1: {k: np.empty((U, U, N0, N1), dtype=NPDOUBLE) for k in keys}, widen)
         if widen:
             out['region'] = (s0, s1)
-        if self._masked_admitted():                                 # every pixel is computed: what match() would have skipped is marked
+        if self._marks_covered():                                   # every pixel is computed: what match() would have skipped is marked
             out['covered'] = self._covered(s0, s1)
         return out
 
@@ -643,7 +667,7 @@ class UMPAModelBase:
         out['shift'] = np.stack([out.pop('si'), out.pop('sj')], axis=1)
         if widen:
             out['region'] = (s0, s1)
-        if self._masked_admitted():
+        if self._marks_covered():
             out['covered'] = self._covered(s0, s1)
         return out
 
@@ -743,7 +767,7 @@ class UMPAModelBase:
         else:
             out['shift'] = np.stack([si, sj], axis=0)
             out['err'] = np.maximum(err, 0)
-        if self._masked_admitted():
+        if self._marks_covered():
             out['covered'] = self._covered(s0, s1)
         return out
 
@@ -835,9 +859,39 @@ class UMPAModelBase:
         else:
             res['shift'] = np.stack([si, sj], axis=0)
             res['err'] = np.maximum(err, 0)
-        if self._masked_admitted():
+        if self._marks_covered():
             res['covered'] = self._covered(s0, s1)
         return res
+
+    _general_grid = False
+
+    @property
+    def general_grid(self):
+        """The opt-in switch of the grid consumers for everything the tiled paths do not take whole (extension;
+        ``include/umpa_grid.h``: ``umpa_grid_set_general``), ``False`` by default.  While it is ``False``, ``match(search='grid')``,
+        ``cost_volume``, ``basins``, ``track`` and ``sequence`` (and ``Tracker``, ``Sequence``, ``match_smooth``) refuse what they always
+        refused, with the same texts.  Set to ``True``, they also take frames at different positions (``pos_list``, sample stepping)
+        or of unequal shapes, a model forced onto the direct kernel, a masked model whose ``masked_grid`` is off or that the masked
+        path does not admit, and steps and search ranges past the tiled limits: the library fills a table of finished costs
+        by the reference's own window x frame sum -- ``cost(i, j, sx, sy)`` bit for bit, at about 38 times the tiled path's
+        arithmetic per pixel -- and the same consumers run on it.  What a tiled path takes whole keeps going there.
+        Where coverage is not trivial, ``match(search='grid')`` skips the pixels below the coverage threshold as ``match()`` does; the
+        others compute every pixel (NaN costs where no frame contributes) and return one more key, ``covered``.  ``widen > 0``,
+        ``coarse_to_fine`` and ``scale_space`` are refused on a model that goes this way: a finished cost is not linear in the
+        windowed sums.  Not on the kernel dark-field model (it has no per-shift table), not on the CPU library."""
+        return bool(self._general_grid)
+
+    @general_grid.setter
+    def general_grid(self, on):
+        on = bool(on)
+        if on and self._kind == KIND_DFKERNEL:
+            raise RuntimeError("general_grid: the kernel dark-field model has no shift table")
+        if on and not self._lib.is_hip:
+            raise RuntimeError("general_grid: it runs on the HIP library only")
+        if self._lib.is_hip and self._kind != KIND_DFKERNEL and getattr(self, "_handle", None) is not None:
+            always = 2 if on and self._force & _lib.F_FORCE_DIRECT else 0
+            _lib.grid().check(_lib.grid().set_general(self._handle, (1 | always) if on else 0), "grid set_general")
+        self._general_grid = on
 
     _force = 0
     _use_staged = False
@@ -1046,7 +1100,8 @@ class _UMPAModelPlain(UMPAModelBase):
     def match(self, step=None, dxdy=None, ROI=None, num_threads=None, quiet=False, search='walk', widen=0):
         """``search='walk'`` (default): the reference's minimiser.  ``search='grid'`` (extension): the global minimum over
         all ``(2 max_shift - 1)^2`` integer shifts, then the same sub-pixel step around it (``include/umpa_grid.h``);
-        no ``pos_list``, no ``dxdy``; a model with masks only with ``masked_grid`` switched on.
+        no ``dxdy``; a model with masks only with ``masked_grid`` switched on, ``pos_list`` (sample stepping), unequal frame
+        shapes and a forced direct kernel only with ``general_grid`` switched on.
 
         ``widen=b`` (1 to 8, with ``search='grid'``; also on ``cost_volume``, ``basins`` and ``track``): window widening
         (``include/umpa_grid.h``).  The shift table and the maps are averaged over the ``(2b + 1)^2`` dense pixels around each
@@ -1072,7 +1127,10 @@ class _UMPAModelPlain(UMPAModelBase):
         Models the plain tiled path takes whole only (no masks, no ``pos_list``, steps and search ranges within its
         limits); anything else raises ``RuntimeError``.  A model with masks is taken once ``masked_grid`` is switched on: every
         pixel of the region is computed (NaN where a window has no pair weight) and the result has one more key,
-        ``covered``.  ``widen``: as for ``match()``; not on a masked model."""
+        ``covered``.  With ``general_grid`` switched on, everything else the walk takes is taken too -- ``pos_list``, unequal frame
+        shapes, any masked model, a forced direct kernel, larger steps -- on a table filled by the explicit window x frame sum;
+        where coverage is not trivial the result has ``covered`` as well.  ``widen``: as for ``match()``; not on a masked model
+        nor on the general table."""
         return self._cost_volume(ROI=ROI, step=step, with_fit=with_fit, widen=widen)
 
     def basins(self, k=4, ROI=None, step=None, widen=0):
