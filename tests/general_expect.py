@@ -101,6 +101,7 @@ def hp_of(sam, ref, pos, Nw, ms, kind, assign, masks=None, pixels=None):
     sh = np.arange(U) - ms + 1
     out = {k: np.full((U, U) + xi.shape, np.nan, dtype=LD) for k in ("cost", "T", "bound")}
     out["df"] = np.full((U, U) + xi.shape, np.nan, dtype=LD) if kind else None
+    out["df_bound"] = np.full((U, U) + xi.shape, np.nan, dtype=LD) if kind else None      # hp_cells' a-priori RELATIVE bound of df
     for s in np.unique(sets):
         if s == 0:
             continue
@@ -119,6 +120,7 @@ def hp_of(sam, ref, pos, Nw, ms, kind, assign, masks=None, pixels=None):
         out["T"][:, :, sel] = r["T"].reshape(shape)
         if kind:
             out["df"][:, :, sel] = r["df"].reshape(shape)
+            out["df_bound"][:, :, sel] = r["df_bound"].reshape(shape)
     out["sets"] = sets
     for v in out.values():
         if v is not None:
@@ -259,3 +261,224 @@ def within_bound(got, v, what):
     worst = float(ratio[fin].max()) if fin.any() else 0.0
     assert worst <= 1.0, "%s: max |gpu - hp| / bound = %.4f" % (what, worst)
     return worst
+
+
+# ----------------------------------------------------------------------------- the LDS geometry (umpa_general_geom.h)
+
+LDS_LIMIT = 64 * 1024
+
+
+def lds_geometry(Nw, ms, step0, step1, masked, ref_mode, by=16, bx=16):
+    """general_footprints restated: ("staged" | "fallback", LDS bytes; 0 where a box side passes 4096 and nothing is computed)"""
+    boxr, boxc = (by - 1) * step0 + 1, (bx - 1) * step1 + 1
+    wide = Nw + (ms - 1 if ms > 1 else 0)
+    if boxr + 2 * wide > 4096 or boxc + 2 * wide > 4096:
+        return "fallback", 0
+    hq, hr = (wide, Nw) if ref_mode else (Nw, wide)
+    even = lambda n: (n + 1) & ~1
+    offR = even((boxr + 2 * hq) * (boxc + 2 * hq))
+    offM = even(offR + (boxr + 2 * hr) * (boxc + 2 * hr))
+    offW = even(offM + ((boxr + 2 * wide) * (boxc + 2 * wide) if masked else 0))
+    nbytes = 8 * (offW + (2 * Nw + 1) ** 2 + 2)
+    return ("staged" if nbytes <= LDS_LIMIT else "fallback"), nbytes
+
+
+# (Nw, ms, step0, step1, masked, ref_mode) -> what tests/general_addr_check.cpp printed for it (the program is the authority; the
+# CPU test holds the restatement above and this table to its output).  The first three are the issue's worked cases.
+LDS_CASES = [
+    ((1, 2, 4, 4, 0, 0), ("fallback", 65656)), ((1, 2, 4, 3, 0, 0), ("staged", 50280)), ((1, 2, 3, 4, 0, 0), ("staged", 50280)),
+    ((1, 1, 4, 4, 0, 0), ("staged", 63608)), ((1, 1, 4, 5, 0, 0), ("fallback", 78712)), ((1, 1, 5, 4, 0, 0), ("fallback", 78712)),
+    ((1, 2, 3, 3, 1, 1), ("staged", 58520)), ((1, 2, 3, 4, 1, 1), ("fallback", 76280)), ((1, 2, 2, 3, 0, 0), ("staged", 26760)),
+    ((1, 2, 5, 5, 0, 0), ("fallback", 99960)), ((2, 3, 1, 1, 1, 0), ("staged", 12632)), ((8, 9, 1, 1, 1, 1), ("staged", 47384)),
+    ((8, 9, 2, 2, 1, 1), ("fallback", 83528)), ((8, 9, 2, 1, 1, 1), ("staged", 62744)), ((0, 1, 5, 5, 0, 0), ("fallback", 92440)),
+    ((0, 1, 6, 5, 0, 0), ("fallback", 110680)), ((1, 3, 273, 1, 0, 0), ("fallback", 0)), ((1, 3, 1, 273, 1, 1), ("fallback", 0)),
+]
+# the GPU cases either side of the limit, taken from that list: (Nw, ms, kind, assign, masked, staged step, fallback step)
+LIMIT_CASES = [
+    (1, 2, 0, "sam", False, (4, 3), (4, 4)),
+    (1, 2, 1, "sam", False, (3, 4), (4, 4)),
+    (1, 1, 0, "sam", False, (4, 4), (4, 5)),                          # max_shift 1: U = 1, a pass is one valid set and three aliases
+    (1, 1, 1, "sam", False, (4, 4), (5, 4)),
+    (1, 2, 1, "ref", True, (3, 3), (3, 4)),
+    (1, 2, 0, "ref", True, (3, 3), (3, 4)),
+]
+LIMIT_IDS = ["Nw%d-ms%d-%s-%s-%s" % (c[0], c[1], "DF" if c[2] else "NoDF", c[3], "mask" if c[4] else "plain") for c in LIMIT_CASES]
+LIMIT_COLS = 66
+
+
+def limit_listed(case):
+    """the two steps of a LIMIT_CASES row as LDS_CASES has them: (staged entry, fallback entry)"""
+    Nw, ms, _, assign, masked, st, fb = case
+    table = dict(LDS_CASES)
+    return tuple(table[(Nw, ms, s[0], s[1], int(masked), int(assign == "ref"))] for s in (st, fb))
+
+
+# ----------------------------------------------------------------------------- input regimes
+
+REGIME_NAMES = ("x2^16", "x2^-5", "counts200", "vis1e-2", "vis1e-3", "zero_mean")
+EDGE26 = {0: (1, 3, 26, 64, 0, "ref", True), 1: (1, 3, 26, 70, 1, "sam", False)}     # the two 26-frame rows of EDGE_CASES
+INSTANCES = [(0, False), (0, True), (1, False), (1, True)]           # general_table_kernel<KIND, MASK>
+
+
+def _regime_cases():
+    """(regime, stack, kind, assign, masked): on D every regime meets the four kernel instantiations, the coordinate mode
+    alternating over them and over the regimes -- and both modes for the two regimes whose costs are the smallest beside
+    their sums, as masked_grid_expect.REGIME_CASES has it; on the 26-frame edge stack the regimes alternate between its two
+    rows of EDGE_CASES"""
+    out = []
+    for q, r in enumerate(REGIME_NAMES):
+        for n, (kind, masked) in enumerate(INSTANCES):
+            modes = ("sam", "ref") if r in ("vis1e-3", "zero_mean") else (("sam", "ref")[(q + n) % 2],)
+            out += [(r, "D", kind, a, masked) for a in modes]
+        e = EDGE26[q % 2]
+        out.append((r, "edge", e[4], e[5], e[6]))
+    return out
+
+
+REGIME_CASES = _regime_cases()
+REGIME_IDS = ["%s-%s-%s-%s-%s" % (r, s, "DF" if k else "NoDF", a, "mask" if mk else "plain") for r, s, k, a, mk in REGIME_CASES]
+
+
+# REGIME_IDS entry -> finite cells whose a-priori relative bound of an fp64 df (hp_cells' df_bound) is above the parity bar
+# of 1e-5, counted from extended precision alone (tests/test_general_regimes_cpu.py holds the table to it; every other
+# dark-field case has none).  On those cells a numerator of df cancels and df is held to model.cost alone; at visibility 1e-3
+# they are 6 % of the volume.
+DF_LOOSE = {
+    "x2^16-D-DF-ref-mask": 1, "x2^-5-D-DF-sam-mask": 1,
+    "vis1e-2-D-DF-ref-plain": 142, "vis1e-2-D-DF-sam-mask": 104, "vis1e-2-edge-DF-sam-plain": 245,
+    "vis1e-3-D-DF-sam-plain": 13500, "vis1e-3-D-DF-ref-plain": 13402, "vis1e-3-D-DF-sam-mask": 12927, "vis1e-3-D-DF-ref-mask": 12828,
+}
+
+
+def apply_regime(regime, sam, ref):
+    """a tests/regimes.py generator on lists of frames of unequal shapes: each stack as one array (a generator reads a stack's
+    values and its mean, never its shape), cut back into the frames"""
+    import regimes as RG
+    flat = lambda fs: np.concatenate([np.asarray(f).ravel() for f in fs])
+    s, r = RG.REGIMES[regime](flat(sam), flat(ref), None)
+    cut = lambda x, fs: [np.ascontiguousarray(a.reshape(f.shape)) for a, f in zip(np.split(x, np.cumsum([f.size for f in fs])[:-1]), fs)]
+    s, r = cut(s, sam), cut(r, ref)
+    frozen(*s, *r)
+    return s, r
+
+
+@functools.lru_cache(maxsize=None)
+def regime_inputs(regime, stack):
+    """(sam, ref, pos, Nw, ms, masks): D, or the 26-frame edge stack of the regime's row, under the regime"""
+    if stack == "D":
+        sam, ref, pos, Nw, ms = D()
+        masks = D_masks()
+    else:
+        Nw, ms, Na, N1 = EDGE26[REGIME_NAMES.index(regime) % 2][:4]
+        sam, ref, pos, masks = edge_inputs(Nw, ms, Na, N1)
+    s, r = apply_regime(regime, sam, ref)
+    return s, r, pos, Nw, ms, masks
+
+
+@functools.lru_cache(maxsize=4)
+def regime_hp(regime, stack, kind, assign, masked):
+    sam, ref, pos, Nw, ms, masks = regime_inputs(regime, stack)
+    return hp_of(sam, ref, pos, Nw, ms, kind, assign, masks=masks if masked else None)
+
+
+def pixel_sample(shapes, pos, pad):
+    """D_sample's rule on any stack: the corners of every frame-set cell, the extent's corners and the workgroup seam"""
+    sets = frame_sets(shapes, pos, pad)
+    N0, N1 = sets.shape
+    px = {(0, 0), (0, N1 - 1), (N0 - 1, 0), (N0 - 1, N1 - 1), (min(15, N0 - 1), 15), (min(16, N0 - 1), 16)}
+    for s in np.unique(sets):
+        r, c = np.nonzero(sets == s)
+        px |= {(r.min(), c[r == r.min()].min()), (r.min(), c[r == r.min()].max()), (r.max(), c[r == r.max()].min()),
+               (r.max(), c[r == r.max()].max())}
+    px = sorted((int(a), int(b)) for a, b in px)
+    return np.array([p[0] for p in px]), np.array([p[1] for p in px])
+
+
+# ----------------------------------------------------------------------------- bad pixels on D
+
+# name -> (frame, row, col in the frame).  D's frame 1 is 64 x 72 at (0, 12), frame 0 64 x 72 at (0, 0).  seam: image pixel
+# (22, 34) = output pixel (16, 28) -- row 16 is a workgroup seam; column 32, the other seam, lies inside its window's reach.
+# The last column is frame 0's: the extent ends before a pixel whose window reaches frame 1's.
+BAD_POSITIONS = {"interior": (1, 30, 25), "seam": (1, 22, 22), "row0": (1, 0, 30), "col0": (1, 30, 0), "last_row": (1, 63, 30),
+                 "last_col": (0, 30, 71)}
+
+
+def bad_hit(where, assign, k, r, c):
+    """[U, U, N0, N1] bool: the entries of D's volume whose window over the `where` stack, in frame k, holds the frame's
+    pixel (r, c) while frame k contributes to the pixel.  The window that moves with the shift is the reference's in 'sam'
+    mode (centre i + s) and the sample's in 'ref' mode (centre i - s); the other stays on the pixel."""
+    sam, _, pos, Nw, ms = D()
+    pad, U = Nw + ms, 2 * ms - 1
+    contrib = contributes([f.shape for f in sam], pos, pad)[k]
+    N0, N1 = contrib.shape
+    xi, xj = np.meshgrid(np.arange(N0), np.arange(N1), indexing="ij")
+    hit = np.zeros((U, U, N0, N1), dtype=bool)
+    moves = (where == "ref") if assign == "sam" else (where == "sam")
+    sign = 1 if assign == "sam" else -1
+    for a in range(U):
+        for b in range(U):
+            si, sj = (sign * (a - ms + 1), sign * (b - ms + 1)) if moves else (0, 0)
+            ci, cj = xi + pad + si - pos[k][0], xj + pad + sj - pos[k][1]
+            hit[a, b] = contrib & (np.abs(ci - r) <= Nw) & (np.abs(cj - c) <= Nw)
+    return hit
+
+
+def bad_frames(value, where, name):
+    """D with `value` written at BAD_POSITIONS[name] of frame k of the `where` stack: (sam, ref)"""
+    import regimes as RG
+    sam, ref = D()[:2]
+    out = {"sam": [f.copy() for f in sam], "ref": [f.copy() for f in ref]}
+    k, r, c = BAD_POSITIONS[name]
+    out[where][k][r, c] = RG.BAD_VALUES[value]
+    return out["sam"], out["ref"]
+
+
+def bad_masks(weight, name):
+    """D_masks() with `weight` at the bad pixel"""
+    masks = [m.copy() for m in D_masks()]
+    k, r, c = BAD_POSITIONS[name]
+    masks[k][r, c] = weight
+    return masks
+
+
+# ----------------------------------------------------------------------------- what the masked path refuses (both switches on)
+
+# which -> (Nw, ms, frames, columns): one frame with Nw 1 (exact fit: 1 x 9 <= 9), and a window half-width the masked table
+# kernel has no configuration for (umpa_tiled.h: 1 to 8)
+REFUSED = {"exact fit": (1, 2, 1, 40), "no configuration": (9, 2, 2, 40)}
+REFUSED_MASK_SEED = 43            # (a seed under which no cell of either volume is rank-deficient: test_general_regimes_cpu.py)
+
+
+@functools.lru_cache(maxsize=None)
+def refused_inputs(which):
+    """(sam, ref, masks, Nw, ms): EDGE_ROWS x 40 output pixels, all frames at (0, 0), 5 % of the mask pixels zero"""
+    from umpa_amd.synth import make_stack
+    Nw, ms, Na, N1 = REFUSED[which]
+    pad = Nw + ms
+    sam, ref, _ = make_stack(EDGE_ROWS + 2 * pad, N1 + 2 * pad, Na, ms, df=True, seed=40 + Nw, amplitude=0.8, order=1)
+    mask = (np.random.default_rng(REFUSED_MASK_SEED).random(sam.shape) >= 0.05).astype(np.float64)
+    frozen(sam, ref, mask)
+    return sam, ref, mask, Nw, ms
+
+
+@functools.lru_cache(maxsize=None)
+def refused_hp(which, kind):
+    sam, ref, mask, Nw, ms = refused_inputs(which)
+    return hp_of(list(sam), list(ref), [(0, 0)] * len(sam), Nw, ms, kind, "sam", masks=list(mask))
+
+
+# ----------------------------------------------------------------------------- D under weighted masks
+
+@functools.lru_cache(maxsize=None)
+def D_weights():
+    """real-valued masks on D: uniform in (0, 1), 5 % of the pixels zero.  The pair weight ma mb / (ma + mb + 1e-8) then takes
+    a different value at every window element -- under D_masks() it only ever takes 0 and 1 / (2 + 1e-8), which is blind to
+    how the reciprocal is formed (pair_weight against pair_weight_fast, umpa_cost.h)"""
+    rng = np.random.default_rng(16)
+    return frozen(*[rng.uniform(0.0, 1.0, size=f.shape) * (rng.random(f.shape) >= 0.05) for f in D()[0]])
+
+
+@functools.lru_cache(maxsize=None)
+def D_hp_weighted(kind, assign):
+    sam, ref, pos, Nw, ms = D()
+    return hp_of(sam, ref, pos, Nw, ms, kind, assign, masks=D_weights())

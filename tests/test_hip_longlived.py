@@ -19,7 +19,9 @@ staged stack is adopted by the FIRST call that reads the sample stack, whichever
 The table's later consumers are steps of the harness too -- ``basins()``, ``track()``, ``sequence()``, ``widen=b`` on the grid
 search, the volume, ``basins`` and ``track``, ``widen.coarse_to_fine``, ``levels.scale_space``, ``uncertainty(resident=True)`` --
 and the ``masked_grid`` switch is a mutation of the record; their trajectories, and those of ``Tracker`` and ``Sequence``, are
-in ``test_hip_longlived_consumers.py``.  Where such a call takes HIP tensors (priors, states, ``out=``) the live model is given
+in ``test_hip_longlived_consumers.py``.  The ``general_grid`` switch and the forced path are mutations of the record as well
+(``set_general``, ``set_force``): the trajectories of the consumers on the general shift table are in
+``test_hip_longlived_general.py``.  Where such a call takes HIP tensors (priors, states, ``out=``) the live model is given
 tensors, the twin the same numbers as host arrays, and the downloaded maps are compared.
 
 Each trajectory prints one line (steps compared, paths seen) for the record.
@@ -93,6 +95,14 @@ def _assert_same(got, want, need, what):
                 what, k, int(bad.sum()), bad.size, first, got[k][first], want[k][first]))
 
 
+def _frames(x):
+    """a stack as the record keeps it: one array, or a list of arrays where the frames' shapes differ"""
+    if isinstance(x, np.ndarray):
+        return np.ascontiguousarray(x)
+    x = [np.ascontiguousarray(f) for f in x]
+    return np.ascontiguousarray(x) if len({f.shape for f in x}) == 1 else x
+
+
 class LongLived:
     """One model that stays alive, and the record a fresh twin is built from.
 
@@ -105,9 +115,9 @@ class LongLived:
         """borrowed: the model borrows device frames (the planes of one tensor per stack), `write` rewrites them in place, and
         the twin is a fresh borrowed model on device copies of the record"""
         self.ns, self.label, self.borrowed = hip_ns, label or cls, borrowed
-        self.rec = dict(cls=cls, sam=("host", np.ascontiguousarray(sam)), ref=np.ascontiguousarray(ref), mask=mask, pos=pos,
+        self.rec = dict(cls=cls, sam=("host", _frames(sam)), ref=_frames(ref), mask=mask, pos=pos,
                         window_size=window_size, max_shift=max_shift, Nw=None, assign="sam", subpx=-1, debug=True, ROI=None,
-                        force=force, unwarp=None, masked_grid=False)
+                        force=force, unwarp=None, masked_grid=False, general_grid=False)
         self.adopted = self.rec["sam"]                                # the stack the library matches: a staged one is not, yet
         self.live = self._construct()
         self.steps, self.paths = 0, []
@@ -125,7 +135,8 @@ class LongLived:
         if self.borrowed:
             m = getattr(self.ns, r["cls"])(_device_frames(np.array(payload)), _device_frames(np.array(r["ref"])), **kw)
         else:
-            m = getattr(self.ns, r["cls"])(payload if kind == "host" else np.zeros_like(r["ref"]), r["ref"], **kw)
+            blank = [np.zeros_like(f) for f in r["ref"]] if isinstance(r["ref"], list) else np.zeros_like(r["ref"])
+            m = getattr(self.ns, r["cls"])(payload if kind == "host" else blank, r["ref"], **kw)
         m._force = r["force"]
         if r["Nw"] is not None:
             m.Nw = r["Nw"]
@@ -136,6 +147,8 @@ class LongLived:
             m.ROI = r["ROI"]
         if r["masked_grid"]:
             m.masked_grid = True
+        if r["general_grid"]:
+            m.general_grid = True
         if kind == "staged":
             raw, dark, flat = payload
             if r["unwarp"] is not None:
@@ -156,19 +169,30 @@ class LongLived:
         assert self.live.masked_grid is bool(on)
         self.rec["masked_grid"] = bool(on)
 
+    def set_general(self, on):
+        """the general_grid switch: the grid consumers of what no tiled path takes whole run on the general table"""
+        self.live.general_grid = on
+        assert self.live.general_grid is bool(on)
+        self.rec["general_grid"] = bool(on)
+
+    def set_force(self, flags):
+        """the forced path (F_FORCE_DIRECT, F_FORCE_TILED, 0); the next consumer call re-derives the library's state from it"""
+        self.live._force = flags
+        self.rec["force"] = flags
+
     def update(self, sam=None, ref=None):
         self.live.update_frames(sam_list=sam, ref_list=ref)
         if sam is not None:
-            self.rec["sam"] = self.adopted = ("host", np.ascontiguousarray(sam))
+            self.rec["sam"] = self.adopted = ("host", _frames(sam))
         if ref is not None:
-            self.rec["ref"] = np.ascontiguousarray(ref)
+            self.rec["ref"] = _frames(ref)
 
     def stage(self, raw, dark=None, flat=None):
         """float64 raws without dark / flat and without a map are copied as they are: the twin is BUILT with them (exact);
         anything else goes through a kernel, and the twin stages the same raws into its own fresh model"""
         self.live.stage_sample(list(raw), dark=dark, flat=flat)
-        plain = raw.dtype == np.float64 and dark is None and flat is None and self.rec["unwarp"] is None
-        self.rec["sam"] = ("host", np.ascontiguousarray(raw)) if plain else ("staged", (raw, dark, flat))
+        plain = all(f.dtype == np.float64 for f in raw) and dark is None and flat is None and self.rec["unwarp"] is None
+        self.rec["sam"] = ("host", _frames(raw)) if plain else ("staged", (raw, dark, flat))
 
     def write(self, sam=None, ref=None):
         """a borrowed model's stacks rewritten where they lie: the addresses stay, the contents change"""
@@ -263,9 +287,24 @@ class LongLived:
     def _fit(self):
         return ("f", "T", "dx", "dy", "err") + (("df",) if self.rec["cls"] == "UMPAModelDF" else ())
 
+    def _goes_general(self):
+        """from the record alone: with general_grid on, a model that no tiled path takes whole -- masks that masked_grid does
+        not admit, frames at different positions or of different shapes, a forced direct kernel"""
+        from umpa_amd import _lib
+        r = self.rec
+        return r["general_grid"] and ((r["mask"] is not None and not r["masked_grid"]) or not self._one_box()
+                                      or bool(r["force"] & _lib.F_FORCE_DIRECT))
+
+    def _one_box(self):
+        if isinstance(self.rec["ref"], list):                         # (_frames: a list where the shapes differ)
+            return False
+        return self.rec["pos"] is None or all(int(p[0]) == 0 and int(p[1]) == 0 for p in self.rec["pos"])
+
     def _extra(self, kw):
-        """`region` of a widened call; `covered` of a masked model with the switch on"""
-        return (("region",) if kw.get("widen") else ()) + (("covered",) if self.rec["masked_grid"] else ())
+        """`region` of a widened call; `covered` of a masked model with the switch on, and of a model that goes the general
+        way with a coverage that is not trivial (masks, or frames at different positions)"""
+        covered = self.rec["masked_grid"] or (self._goes_general() and (self.rec["mask"] is not None or not self._one_box()))
+        return (("region",) if kw.get("widen") else ()) + (("covered",) if covered else ())
 
     def grid(self, what="", expect_path=None, **kw):
         """match(search='grid', **kw), `region` of a widened call included"""

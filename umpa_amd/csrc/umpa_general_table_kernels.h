@@ -32,6 +32,7 @@
 // A pixel no frame contributes to gets what eval_direct gives it: 0 / 0, NaN costs.
 #pragma once
 #include "umpa_direct.h"
+#include "umpa_general_geom.h"
 
 namespace umpa {
 
@@ -48,21 +49,14 @@ struct GeneralArgs {
 // hence no cap on their rows and columns other than the 64 KiB of LDS a kernel gets without asking
 inline bool general_geometry(const ModelDev& m, bool has_mask, const RegionArgs& A, StagedGeom& G, size_t& lds_bytes)
 {
-    const long boxr = (long)(UMPA_STAGED_BY - 1) * A.step0 + 1, boxc = (long)(UMPA_STAGED_BX - 1) * A.step1 + 1;
-    const int wide = m.Nw + (m.ms > 1 ? m.ms - 1 : 0);
-    if (boxr + 2 * wide > 4096 || boxc + 2 * wide > 4096) return false;
-    G.hq = m.ref_mode ? wide : m.Nw;                                  // the sample window moves in 'ref' mode (Model.cpp:688-701)
-    G.hr = m.ref_mode ? m.Nw : wide;
-    G.hm = wide;
-    G.rowsQ = (int)boxr + 2 * G.hq; G.colsQ = (int)boxc + 2 * G.hq;
-    G.rowsR = (int)boxr + 2 * G.hr; G.colsR = (int)boxc + 2 * G.hr;
-    G.rowsM = has_mask ? (int)boxr + 2 * G.hm : 0; G.colsM = has_mask ? (int)boxc + 2 * G.hm : 0;
-    G.offR = (G.rowsQ * G.colsQ + 1) & ~1;
-    G.offM = (G.offR + G.rowsR * G.colsR + 1) & ~1;
-    G.offW = (G.offM + G.rowsM * G.colsM + 1) & ~1;
-    const int S = 2 * m.Nw + 1;
-    lds_bytes = (size_t)(G.offW + S * S + 2) * sizeof(double);
-    return lds_bytes <= (size_t)64 * 1024;
+    GeneralFootprints F;                                              // umpa_general_geom.h: the arithmetic, on plain ints
+    const bool fits = general_footprints(m.Nw, m.ms, m.ref_mode, has_mask, A.step0, A.step1, UMPA_STAGED_BY, UMPA_STAGED_BX, F);
+    if (!F.lds_bytes) return false;                                   // (a box past UMPA_GENERAL_MAX_SIDE: G and lds_bytes stay)
+    lds_bytes = F.lds_bytes;
+    G.hq = F.hq; G.hr = F.hr; G.hm = F.hm;
+    G.rowsQ = F.rowsQ; G.colsQ = F.colsQ; G.rowsR = F.rowsR; G.colsR = F.colsR; G.rowsM = F.rowsM; G.colsM = F.colsM;
+    G.offR = F.offR; G.offM = F.offM; G.offW = F.offW;
+    return fits;
 }
 
 template <int KIND, bool MASK>
@@ -98,6 +92,9 @@ general_table_kernel(ModelDev m, RegionArgs A, GeneralArgs T, StagedGeom G)
     double* fr = fq + G.offR;
     double* fm = fq + G.offM;
     double* wl = fq + G.offW;                                         // the window: every lane reads the same weight (LDS broadcast)
+    // The index arithmetic from here on -- the box origin, q0 / r0 / mq0 / mr0, dc and the clamped source of a staged element --
+    // is restated term for term in umpa_general_geom.h (general_box_origin, general_window_origin, general_set_offset,
+    // general_source), which tests/general_addr_check.cpp sweeps on the host: change one and change the other.
     const int gi0 = A.org0 + A.step0 * (T.row0 + blockIdx.y * UMPA_STAGED_BY), gj0 = A.org1 + A.step1 * (blockIdx.x * UMPA_STAGED_BX);   // box origin
     const int Nw = m.Nw, S = 2 * Nw + 1, pad = m.padding;
     for (int q = tid; q < S * S; q += UMPA_STAGED_THREADS) wl[q] = gp(m.win)[q];   // (read behind the first frame's barriers)
@@ -109,14 +106,14 @@ general_table_kernel(ModelDev m, RegionArgs A, GeneralArgs T, StagedGeom G)
             // nearer (sample, 'ref' mode)
             int ri = i, rj = j, qi = i, qj = j;                      // Model.cpp:408-421 / :688-701
             if (m.ref_mode) { qi -= si; qj -= sj0; } else { ri += si; rj += sj0; }
-            const int q0 = (qi - Nw - (gi0 - G.hq)) * G.colsQ + (qj - Nw - (gj0 - G.hq));
+            const int q0 = (qi - Nw - (gi0 - G.hq)) * G.colsQ + (qj - Nw - (gj0 - G.hq));     // general_window_origin (umpa_general_geom.h)
             const int r0 = (ri - Nw - (gi0 - G.hr)) * G.colsR + (rj - Nw - (gj0 - G.hr));
             const int mq0 = (qi - Nw - (gi0 - G.hm)) * G.colsM + (qj - Nw - (gj0 - G.hm));
             const int mr0 = (ri - Nw - (gi0 - G.hm)) * G.colsM + (rj - Nw - (gj0 - G.hm));
             int dq[CJ], dr[CJ];
 #pragma unroll
             for (int c = 0; c < CJ; c++) {
-                const int dc = min(c, ms - 1 - sj0);
+                const int dc = min(c, ms - 1 - sj0);                  // general_set_offset (umpa_general_geom.h)
                 dq[c] = m.ref_mode ? -dc : 0;
                 dr[c] = m.ref_mode ? 0 : dc;
             }
@@ -132,7 +129,7 @@ general_table_kernel(ModelDev m, RegionArgs A, GeneralArgs T, StagedGeom G)
                 __syncthreads();                                      // the previous frame's footprints have been read
                 // ---- footprints of frame k.  Frame coordinates = image coordinates - position, clamped at the frame
                 // edges: every address lies inside the frame, and what is clamped is never read by a lane the frame
-                // contributes to.
+                // contributes to.  The clamp is general_source's (umpa_general_geom.h).
                 {
                     const int fi0 = gi0 - f.pi, fj0 = gj0 - f.pj;
                     for (int q = tid; q < G.rowsQ * G.colsQ; q += UMPA_STAGED_THREADS) {
