@@ -55,11 +55,12 @@ extern "C" {
 #define UMPA_HIP_F_FORCE_DIRECT   2  /* use the general direct kernel even where the tiled fast path applies */
 #define UMPA_HIP_F_FORCE_TILED    4  /* fail with E_UNSUPPORTED instead of silently using the direct kernel */
 #define UMPA_HIP_F_PLANAR         8  /* values is [nparam][N0*N1] (one plane per map) instead of the reference's [N0*N1][nparam] */
-#define UMPA_HIP_F_REUSE_REF_MAPS 16 /* the reference stack is the one of this model's previous match (match_unbiased, a projection
-                                        series against one reference): the tiled path keeps its reference-side maps and recomputes
-                                        only the sample side.  For frames the model owns it also checks that itself
-                                        (umpa_hip_update_frames / set_window invalidate); for borrowed device frames the caller vouches.
-                                        Results are identical with and without. */
+#define UMPA_HIP_F_REUSE_REF_MAPS 16 /* borrowed device frames (UMPA_HIP_F_DEVICE_FRAMES) only: the caller vouches that it has not
+                                        written the reference stack since this model's previous match, so the tiled path keeps its
+                                        reference-side maps and recomputes only the sample side.  For frames the model owns nothing
+                                        needs saying: the library is the only writer (umpa_hip_update_frames, which drops the maps,
+                                        as umpa_hip_set_window does), every match reuses what it can, and the flag changes nothing.
+                                        Results are identical with and without; the first match of a model computes both sides. */
 
 #define UMPA_HIP_F_USE_STAGED      32 /* the stack uploaded by umpa_hip_stage_sample becomes the sample stack of this match (of this
                                          volume, for umpa_grid_cost_volume) and stays it; without a staged stack: UMPA_HIP_E_ARG */

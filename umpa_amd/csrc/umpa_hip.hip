@@ -532,8 +532,10 @@ int run_tiled(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int fla
 {
     TiledTimers tt(m->timing ? &m->launches : nullptr, [m]() { return get_event(m); }, s);
     ModelDev dev = m->dev();
-    if (sub) { dev.frames = sub->frames; dev.Na = sub->n; m->tiled.ref_maps_ok = false; }      // (Nwt stays the model's frame count)
-    const bool reuse = !sub && (flags & UMPA_HIP_F_REUSE_REF_MAPS) != 0;
+    if (sub) { dev.frames = sub->frames; dev.Na = sub->n; prep_plan_invalidate(m->tiled); }    // (Nwt stays the model's frame count)
+    // the reference-side maps of the last match are kept where nobody can have written the frames behind them: the
+    // library's own (umpa_hip_update_frames clears the record), or borrowed ones whose owner says so
+    const bool reuse = prep_reuse(sub != nullptr, m->owns_frames, (flags & UMPA_HIP_F_REUSE_REF_MAPS) != 0);
     std::vector<FrameDesc> hf;                                        // a host copy of the frame list (corr_march's staging offsets)
     if (!sub) hf = frame_list(m);
     int rc = m->has_mask
@@ -541,7 +543,7 @@ int run_tiled(umpa_hip_model* m, const RegionArgs& A, const StepGeom& g, int fla
                              tt, reuse, m->mask_binary, piece_rows, on_rows)
         : tiled_match(m->tiled, dev, m->kind, g.Himg, g.Wimg, sub ? sub->box : g.box, A, s,
                       tt, reuse, piece_rows, on_rows, sub ? sub->host : hf.data());
-    if (sub) m->tiled.ref_maps_ok = false;                            // the maps now hold a subset's planes
+    if (sub) prep_plan_invalidate(m->tiled);                          // the maps now hold a subset's planes
     if (rc == -3) return fail(UMPA_HIP_E_NOMEM, "tiled path: device scratch allocation failed");
     if (rc != 0) return fail(UMPA_HIP_E_LAUNCH, "tiled path: launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
     return 0;
@@ -848,7 +850,7 @@ int umpa_hip_update_frames(umpa_hip_model* m, double* const* sam, double* const*
     if (!m) return fail(UMPA_HIP_E_ARG, "null model");
     if (!m->owns_frames) return fail(UMPA_HIP_E_ARG, "the model borrows device frames; update them in place instead");
     HIP_TRY(hipSetDevice(m->device), UMPA_HIP_E_DEVICE);
-    if (ref) m->tiled.ref_maps_ok = false;
+    if (ref) prep_plan_invalidate(m->tiled);                          // the one way the frames the model owns change: no match reuses across it
     // the last stack wins: a stack staged before this call and not adopted yet is dropped (its upload may still be running
     // into the back buffer, which nothing reads before the next umpa_hip_stage_sample)
     if (sam) m->staged = false;

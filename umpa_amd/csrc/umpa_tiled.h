@@ -30,6 +30,7 @@
 #include "umpa_corr.h"
 #include "umpa_march.h"
 #include "umpa_masked.h"
+#include "umpa_prep_plan.h"
 #include <mutex>
 #include <vector>
 #include <functional>
@@ -497,7 +498,7 @@ replay_walk_kernel(ModelDev m, Maps M, ReplayArgs R, RegionArgs A, OdArgs od_in)
 typedef hipError_t (*TableConsumer)(void* user, const ModelDev& dev, const Maps& M, const ReplayArgs& R, const RegionArgs& A,
                                     hipStream_t s);
 
-struct TiledState {
+struct TiledState : RefMapsRecord {    // (the record of the reference-side maps in `maps`: umpa_prep_plan.h)
     TableConsumer consumer = nullptr;  void* consumer_user = nullptr;   // umpa_hipx_set_table_consumer
     bool masked_consumer = false;      // umpa_hipx_set_masked_consumer: a consumer may be handed the masked path's table of finished costs
     double* maps = nullptr;   size_t maps_cap = 0;
@@ -506,12 +507,6 @@ struct TiledState {
     Sep1D sep;
     bool separable = false;
     int sep_nw = -1;
-    // the reference-side maps in `maps` are current for this (kind, frame count, plane size): set by tiled_match,
-    // cleared by whoever changes the reference frames or the window
-    bool ref_maps_ok = false;
-    int ref_kind = -1, ref_K = 0;
-    size_t ref_plane = 0;
-    int ref_rect[4] = {0, 0, 0, 0};   // tiles (tx0, tx1, ty0, ty1) of the maps that were computed (PrepRect)
     // on-demand passes (umpa_ondemand.h): device scratch, and page-locked slots the counters of a timed match land in
     void* od_buf = nullptr;   size_t od_cap = 0;
     int* od_host = nullptr;   int od_slot = 0;
@@ -599,7 +594,7 @@ inline bool tiled_factor_window(TiledState& st, const double* win, int Nw)
 {
     const int S = 2 * Nw + 1;
     st.separable = false;
-    st.ref_maps_ok = false;                                           // every map is a filter with this window
+    prep_plan_invalidate(st);                                         // every map is a filter with this window
     st.sep_nw = Nw;
     if (Nw > UMPA_MAX_NW) return false;
     const double pivot = win[Nw * S + Nw];
@@ -623,7 +618,7 @@ inline void tiled_release(TiledState& st)
     st.maps = st.table = nullptr;
     st.od_buf = nullptr; st.od_host = nullptr; st.od_cap = 0;
     st.maps_cap = st.table_cap = 0;
-    st.ref_maps_ok = false;
+    prep_plan_invalidate(st);
 }
 
 inline int pick_ub(int UJ)
@@ -908,8 +903,7 @@ inline hipError_t launch_march(const ModelDev& dev, MarchArgs A, const Sep1D& se
 
 // The tiles of the maps a region needs: its pixels, seen from the image, and max_shift around them (a map is read at the
 // pixel and at the pixel + shift).  Matches of a part of the image -- a ROI, one rectangle of a sample-stepping stack -- then
-// pay for their part of the maps only.
-struct PrepRect { int tx0, tx1, ty0, ty1; };
+// pay for their part of the maps only.  (PrepRect: umpa_prep_plan.h)
 template <int NW>
 inline PrepRect prep_rect(const Maps& M, const RegionArgs& A, int ms)
 {
@@ -1038,14 +1032,14 @@ inline int tiled_maps(TiledState& st, Maps& M, int kind, int K, int H, int W, co
     const size_t plane = (size_t)H * W;
     const size_t KP = ((size_t)K + 1) / 2;                             // pair planes per stack (Maps)
     const size_t nmaps = kind == 1 ? 2 + 4 * KP : 2;
-    if (st.maps_cap < nmaps * plane) {
+    const bool grow = st.maps_cap < nmaps * plane;
+    prep_plan_layout(st, kind, K, plane, grow);
+    if (grow) {
         if (st.maps) (void)hipFree(st.maps);
         st.maps = nullptr; st.maps_cap = 0;
-        st.ref_maps_ok = false;
         if (hipMalloc((void**)&st.maps, nmaps * plane * sizeof(double)) != hipSuccess) return -3;
         st.maps_cap = nmaps * plane;
     }
-    if (st.ref_kind != kind || st.ref_K != K || st.ref_plane != plane) st.ref_maps_ok = false;
     M.H = H; M.W = W;
     M.br0 = box.r0; M.br1 = box.r1; M.bc0 = box.c0; M.bc1 = box.c1; M.Wf = box.Wf;
     M.SamSq = st.maps; M.RefSq = st.maps + plane;
@@ -1094,17 +1088,15 @@ inline int tiled_table(TiledState& st, const TiledEnv& E, size_t per_row, int N0
     return 0;
 }
 
-// The maps of the tiles the region reads (prep_rect): both sides (3), or `reuse_sides` where the caller vouches for the
-// reference frames (`reuse`) and the reference-side maps cover those tiles -- 1, the sample side (plain path), or 0, nothing
-// (masked path: only the reference means are read).
+// The maps of the tiles the region reads (prep_rect): both sides (3), or `reuse_sides` where the reference frames are
+// known to be those of the last match (`reuse`: prep_reuse) and the reference-side maps cover those tiles -- 1, the sample
+// side (plain path), or 0, nothing (masked path: only the reference means are read).  umpa_prep_plan.h decides.
 inline hipError_t tiled_prep(TiledState& st, const ModelDev& dev, const Maps& M, const RegionArgs& A, int kind, bool reuse,
                              int reuse_sides, hipStream_t s, TiledTimers& tt)
 {
     PrepRect PR = {0, 0, 0, 0};
     UMPA_NW_SWITCH(dev.Nw, (PR = prep_rect<NWC>(M, A, dev.ms)))
-    const bool covered = st.ref_rect[0] <= PR.tx0 && st.ref_rect[1] >= PR.tx1 && st.ref_rect[2] <= PR.ty0 && st.ref_rect[3] >= PR.ty1;
-    const int sides = (reuse && st.ref_maps_ok && covered) ? reuse_sides : 3;
-    st.ref_maps_ok = false;
+    const int sides = prep_plan_sides(st, PR, reuse, reuse_sides);
     if (sides) {
         hipError_t e = hipErrorInvalidValue;
         tt.tic(2);
@@ -1112,9 +1104,8 @@ inline hipError_t tiled_prep(TiledState& st, const ModelDev& dev, const Maps& M,
         else { UMPA_NW_SWITCH(dev.Nw, (e = launch_prep<0, NWC>(dev, M, st.sep, sides, s, PR))) }
         tt.toc();
         if (e != hipSuccess) return e;
-        st.ref_rect[0] = PR.tx0; st.ref_rect[1] = PR.tx1; st.ref_rect[2] = PR.ty0; st.ref_rect[3] = PR.ty1;
     }
-    st.ref_maps_ok = true; st.ref_kind = kind; st.ref_K = dev.Na; st.ref_plane = (size_t)M.H * M.W;
+    prep_plan_done(st, PR, sides, kind, dev.Na, (size_t)M.H * M.W);
     return hipSuccess;
 }
 
@@ -1182,7 +1173,7 @@ inline int tiled_chunk(TiledState& st, const CorrLaunch& CL, bool on_demand, siz
 }
 
 // One match of a region on the tiled path.  Returns 0, -3 (allocation) or a positive hipError_t.
-// `reuse_ref_maps`: the caller vouches that the reference frames are those of the previous call (it owns them).
+// `reuse_ref_maps`: the reference frames are those of the previous call (prep_reuse: the library owns them, or the owner vouches).
 // `piece_rows` > 0: row chunks of at most that many dense rows (a multiple of 32) even where the table budget would
 // allow more (the host-array entry point downloads the rows of chunk c while chunk c+1 is being matched, the multi-GPU
 // leg sends them to rank 0); `on_rows(xi_lo, xi_hi)` is called after the kernels of a chunk have been enqueued.
